@@ -9,6 +9,12 @@ One timed step = one ``collection.update(preds, target)``; every
 
 Output: ONE JSON line on rank 0 with the whole-job aggregate
 metric_updates_per_sec (n_gpus * 16 metrics * steps / max-rank elapsed).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints that line.
+``--dump-outputs DIR`` also writes what ``collection.compute()`` returns after
+the last timed step as ``DIR/<metric>.npy`` (inputs are seeded, so two builds
+can be compared output for output). Everything beyond the headline figure
+(the same-session run of the reference torchmetrics) is behind ``--full``.
 """
 from __future__ import annotations
 
@@ -51,7 +57,7 @@ def _measure_reference_baseline(args) -> float | None:
     """Run the reference torchmetrics bench (same config) in a subprocess.
 
     Returns its metric_updates_per_sec, or None if the staged reference is
-    unavailable. Result (with provenance) lands in gpurun_out/ref_baseline.json.
+    unavailable. Result (with provenance) lands in bench_out/ref_baseline.json.
     """
     import subprocess
 
@@ -69,16 +75,62 @@ def _measure_reference_baseline(args) -> float | None:
         "--compute-every", str(args.compute_every),
     ]
     try:
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=1800)
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
         line = [l for l in out.stdout.strip().splitlines() if l.startswith("{")][-1]
         rec = json.loads(line)
-        os.makedirs("gpurun_out", exist_ok=True)
-        with open("gpurun_out/ref_baseline.json", "w") as fh:
+        os.makedirs("bench_out", exist_ok=True)
+        with open("bench_out/ref_baseline.json", "w") as fh:
             json.dump(rec, fh)
         return float(rec["value"])
     except Exception as err:
         print(f"ref baseline run failed: {err}", file=sys.stderr)
         return None
+
+
+_DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def _flatten_outputs(name, value, out):
+    if isinstance(value, torch.Tensor):
+        out[name] = value
+    elif isinstance(value, dict):
+        for k, v in value.items():
+            _flatten_outputs(f"{name}.{k}", v, out)
+    elif isinstance(value, (list, tuple)):
+        for i, v in enumerate(value):
+            _flatten_outputs(f"{name}.{i}", v, out)
+    else:
+        out[name] = torch.as_tensor(value)
+
+
+def _dump_outputs(result: dict, out_dir: str) -> None:
+    """Write compute()'s result as <out_dir>/<metric>.npy (float32/float64).
+
+    Floating outputs are stored as float32 (float64 stays), integer ones as
+    float64. Where everything together would pass 64 MB, the largest arrays
+    are reduced to a fixed, seeded sample of their flattened elements.
+    """
+    import numpy as np
+
+    flat: dict = {}
+    for name, value in result.items():
+        _flatten_outputs(name, value, flat)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t in flat.items():
+        t = t.detach().cpu()
+        t = t.to(torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32)
+        arrays[name] = t.numpy()
+    # smallest first: each array may use an equal share of what is still free
+    left = _DUMP_BUDGET_BYTES
+    for i, name in enumerate(sorted(arrays, key=lambda n: arrays[n].nbytes)):
+        arr = arrays[name]
+        share = left // (len(arrays) - i)
+        if arr.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, share // arr.itemsize, replace=False))
+            arr = arr.reshape(-1)[idx]
+        left -= arr.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def main() -> None:
@@ -92,13 +144,26 @@ def main() -> None:
     parser.add_argument("--curve-thresholds", type=int, default=200)
     parser.add_argument("--graphs", action="store_true", help="capture the update into a hipGraph (launch-bound configs; the default eager path is faster for this bench shape)")
     parser.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write what collection.compute() returns for the state "
+        "of the last timed step as DIR/<metric>.npy",
+    )
+    parser.add_argument(
+        "--full",
+        action="store_true",
+        help="beyond the headline figure, also run the reference torchmetrics on the same "
+        "config in this session (needs tools/refbench/_staged populated via "
+        "stage_reference.sh) and use that fresh number for vs_baseline",
+    )
+    parser.add_argument(
         "--run-ref-baseline",
         action="store_true",
-        help="also run the reference torchmetrics on the same config in this session "
-        "(needs tools/refbench/_staged populated via stage_reference.sh) and use that "
-        "fresh number for vs_baseline",
+        help="older name of --full",
     )
     args = parser.parse_args()
+    args.full = args.full or args.run_ref_baseline
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -177,6 +242,13 @@ def main() -> None:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
 
+    # the arrays a caller gets from the state the last timed step left
+    # (compute() is collective under RCCL: every rank calls it, rank 0 writes)
+    if args.dump_outputs:
+        outputs = coll.compute()
+        if rank == 0:
+            _dump_outputs(outputs, args.dump_outputs)
+
     # max over ranks
     if distributed:
         t = torch.tensor([elapsed], device=device if use_gpu else "cpu")
@@ -190,8 +262,8 @@ def main() -> None:
     # Baseline: the reference (torchmetrics 1.7.0dev) measured on the SAME
     # config on 1x MI355X via tools/refbench/run_ref_bench.py. BASELINE.json
     # has no published numbers, so this measured same-hardware number is the
-    # comparison point. Pass --run-ref-baseline to re-measure it in the same
-    # session (writes gpurun_out/ref_baseline.json and uses the fresh number).
+    # comparison point. Pass --full to re-measure it in the same session
+    # (writes bench_out/ref_baseline.json and uses the fresh number).
     # The reference's throughput depends on the effective compute cadence
     # (computes are ~15% of its step cost at cadence 5); these were measured
     # at three cadences on MI355X (r2 2026-09-12) so vs_baseline stays
@@ -201,7 +273,7 @@ def main() -> None:
     _nearest = min(_REF_BY_CADENCE, key=lambda k: abs(k - _eff_ce)) if _eff_ce else 32
     REFERENCE_UPDATES_PER_SEC_1GPU = _REF_BY_CADENCE[_nearest]
     baseline_src = f"tools/refbench/run_ref_bench.py r2 2026-09-12 (cadence {_nearest})"
-    if args.run_ref_baseline and rank == 0 and use_gpu:
+    if args.full and rank == 0 and use_gpu:
         fresh = _measure_reference_baseline(args)
         if fresh is not None:
             REFERENCE_UPDATES_PER_SEC_1GPU = fresh

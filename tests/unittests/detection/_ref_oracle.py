@@ -4,20 +4,21 @@ offline oracle for differential mAP fuzzing.
 The legacy reference class only *algorithmically* needs box math for
 iou_type="bbox"; its imports of torchvision/pycocotools are satisfied with
 local stubs (our own implementations of box_area/box_iou/box_convert; mask
-utils raise — segm is never exercised through this oracle). Returns None
-when /root/reference is not present (e.g. on a GPU box) so callers skip.
+utils raise — segm is never exercised through this oracle).
+
+The oracle is loaded only while the golden tapes are recorded (see
+tests/unittests/_golden.py); otherwise load_legacy_map() returns a stand-in
+that replays what the oracle returned then.
 """
 from __future__ import annotations
 
 import importlib.machinery
-import os
 import sys
 import types
 
 import torch
 
-_REF_SRC = "/root/reference/src"
-_SHIM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "..", "tools", "refbench")
+from tests.unittests._golden import ref_object
 
 
 def _box_area(b):
@@ -91,11 +92,10 @@ def _stub(name: str) -> types.ModuleType:
 
 def load_legacy_map():
     """Return the reference's pure-torch MeanAveragePrecision class, or None."""
-    if not os.path.isdir(_REF_SRC):
-        return None
-    if _REF_SRC not in sys.path:
-        sys.path.insert(0, os.path.abspath(_SHIM))
-        sys.path.insert(0, _REF_SRC)
+    return ref_object("legacy MeanAveragePrecision", _load_legacy_map)
+
+
+def _load_legacy_map():
     if "torchvision" not in sys.modules:
         tv = _stub("torchvision")
         tv.__version__ = "0.20.0"

@@ -1,19 +1,20 @@
 """Differential fuzz: our COCO mAP vs the reference's pure-torch COCOeval.
 
-Oracle: /root/reference torchmetrics detection/_mean_ap.py:420-860 (the
-algorithmic spec this implementation was rebuilt from), loaded offline via
-tests/unittests/detection/_ref_oracle.py. Sweeps image counts, class counts,
-empty preds/targets, duplicate detections, area-range diversity (small /
-medium / large boxes), score ties and maxDets saturation. Skips when the
-reference tree is unavailable (e.g. on a GPU box).
+Oracle: torchmetrics detection/_mean_ap.py:420-860 (the algorithmic spec
+this implementation was rebuilt from), loaded via
+tests/unittests/detection/_ref_oracle.py and replayed from the golden tapes
+under tests/golden/reference/. Sweeps image counts, class counts, empty
+preds/targets, duplicate detections, area-range diversity (small / medium /
+large boxes), score ties and maxDets saturation.
 
 Crowd annotations and segm masks are NOT covered here: the legacy reference
 ignores `iscrowd` and its segm path needs pycocotools, which this offline
 environment cannot provide — crowd/segm behavior is covered by the
 hand-built scenario tests in test_mean_ap.py.
 
-Case count: 60 by default, scale with MA_MAP_FUZZ_CASES (a 200-case run is
-recorded in docs/CHANGELOG r2 notes).
+Case count: 60 by default, the cases the tapes hold; MA_MAP_FUZZ_CASES scales
+it while re-recording against a reference tree (a 200-case run is recorded in
+docs/CHANGELOG r2 notes).
 """
 from __future__ import annotations
 
@@ -24,9 +25,10 @@ import torch
 
 from tests.unittests.detection._ref_oracle import load_legacy_map
 
-RefMAP = load_legacy_map()
 
-pytestmark = pytest.mark.skipif(RefMAP is None, reason="reference tree not available for oracle")
+def RefMAP(**kwargs):
+    return load_legacy_map()(**kwargs)
+
 
 _KEYS = [
     "map", "map_50", "map_75", "map_small", "map_medium", "map_large",

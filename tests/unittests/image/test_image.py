@@ -242,19 +242,10 @@ def test_clip_iqa_and_infolm_raise_without_models():
 
 
 def _ref_image_functional(name):
-    """Import a reference functional (offline oracle); None if unavailable."""
-    import os
-    import sys
+    """A reference functional, replayed from tests/golden/reference/."""
+    from tests.unittests._golden import ref_module
 
-    if not os.path.isdir("/root/reference/src"):
-        return None
-    sys.path.insert(0, "/root/repo/tools/refbench")
-    sys.path.insert(0, "/root/reference/src")
-    try:
-        import torchmetrics.functional.image as ref_img
-    except Exception:
-        return None
-    return getattr(ref_img, name)
+    return getattr(ref_module("torchmetrics.functional.image"), name)
 
 
 @pytest.mark.parametrize(
@@ -270,8 +261,6 @@ def _ref_image_functional(name):
 )
 def test_ssim_3d_vs_reference(kwargs):
     ref = _ref_image_functional("structural_similarity_index_measure")
-    if ref is None:
-        pytest.skip("reference tree not available")
     from metrics_amd.functional.image import structural_similarity_index_measure as ours
 
     torch.manual_seed(0)
@@ -287,8 +276,6 @@ def test_ssim_3d_vs_reference(kwargs):
 
 def test_ms_ssim_3d_vs_reference():
     ref = _ref_image_functional("multiscale_structural_similarity_index_measure")
-    if ref is None:
-        pytest.skip("reference tree not available")
     from metrics_amd.functional.image import multiscale_structural_similarity_index_measure as ours
 
     torch.manual_seed(1)

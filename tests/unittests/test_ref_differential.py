@@ -5,32 +5,16 @@ ours and the reference's with IDENTICAL seeded random inputs and compare.
 This is behavioral parity on random data — far stronger than the doctest
 examples, which only pin the documented cases.
 
-Skipped wholesale when /root/reference is unavailable (e.g. GPU boxes).
+The reference side is replayed from the golden tapes under
+tests/golden/reference/ (see tests/unittests/_golden.py).
 """
 from __future__ import annotations
-
-import os
-import sys
 
 import pytest
 import torch
 
-_REF = "/root/reference/src"
-HAVE_REF = os.path.isdir(_REF)
-
-pytestmark = pytest.mark.skipif(not HAVE_REF, reason="reference tree not available")
-
-if HAVE_REF:
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "tools", "refbench"))
-    sys.path.insert(0, _REF)
-
 import metrics_amd.functional as ours_f
-
-
-def _ref_functional():
-    import torchmetrics.functional as ref_f
-
-    return ref_f
+from tests.unittests._golden import ref_module
 
 
 def _g(seed):
@@ -274,13 +258,14 @@ _DOMAINS = (
 )
 
 
-def _resolve(pkg_name, name):
+def _resolve(pkg_name, name, import_module=None):
     import importlib
 
+    import_module = import_module or importlib.import_module
     for sub in _DOMAINS:
         mod_name = pkg_name if not sub else f"{pkg_name}.{sub}"
         try:
-            mod = importlib.import_module(mod_name)
+            mod = import_module(mod_name)
         except Exception:
             continue
         fn = getattr(mod, name, None)
@@ -290,9 +275,8 @@ def _resolve(pkg_name, name):
 
 
 def _run_case(name, gen, kwargs, atol):
-    _ref_functional()
     ours = _resolve("metrics_amd.functional", name)
-    ref = _resolve("torchmetrics.functional", name)
+    ref = _resolve("torchmetrics.functional", name, ref_module)
     if ours is None or ref is None:
         pytest.fail(f"functional {name} missing: ours={ours is not None} ref={ref is not None}")
     for seed in (0, 1, 2):
@@ -424,9 +408,9 @@ def test_ref_differential_wave3(name, gen, kwargs, atol):
     if name == "permutation_invariant_training":
         # needs a callable metric_func on both sides
         from metrics_amd.functional.audio import scale_invariant_signal_noise_ratio as our_m
-        import torchmetrics.functional.audio as ref_a
-
         import metrics_amd.functional.audio as our_a
+
+        ref_a = ref_module("torchmetrics.functional.audio")
 
         p, t = gen(3)
         got = our_a.permutation_invariant_training(p, t, our_m, "speaker-wise", "max")

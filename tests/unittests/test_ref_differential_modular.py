@@ -4,30 +4,21 @@ composition and collections driven with identical batch sequences.
 The functional harness (test_ref_differential.py) pins the math; this one
 pins the STATEFUL layer — forward()-vs-forward() per batch and final
 compute()-vs-compute() — where the wrapper/aggregation logic lives.
+
+The reference side is replayed from the golden tapes under
+tests/golden/reference/ (see tests/unittests/_golden.py).
 """
 from __future__ import annotations
-
-import os
-import sys
 
 import pytest
 import torch
 
-_REF = "/root/reference/src"
-HAVE_REF = os.path.isdir(_REF)
-pytestmark = pytest.mark.skipif(not HAVE_REF, reason="reference tree not available")
-
-if HAVE_REF:
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "tools", "refbench"))
-    sys.path.insert(0, _REF)
-
 import metrics_amd as ma
+from tests.unittests._golden import ref_module, ref_value
 
 
 def _tm():
-    import torchmetrics as tm
-
-    return tm
+    return ref_module("torchmetrics")
 
 
 def _cmp(a, b, atol=1e-5):
@@ -293,7 +284,7 @@ def test_detection_iou_module():
     import importlib
 
     try:
-        ref = importlib.import_module("torchmetrics.detection.iou").IntersectionOverUnion()
+        ref = ref_module("torchmetrics.detection.iou").IntersectionOverUnion()
     except Exception as err:
         pytest.skip(f"reference IoU module unavailable offline: {err}")
     g = torch.Generator().manual_seed(52)
@@ -379,7 +370,7 @@ def test_detection_iou_family(name, kwargs):
     mod_name = {"IntersectionOverUnion": "iou", "GeneralizedIntersectionOverUnion": "giou",
                 "DistanceIntersectionOverUnion": "diou", "CompleteIntersectionOverUnion": "ciou"}[name]
     try:
-        ref_mod = importlib.import_module(f"torchmetrics.detection.{mod_name}")
+        ref_mod = ref_module(f"torchmetrics.detection.{mod_name}")
         ref = getattr(ref_mod, name)(**kwargs)
     except Exception as err:
         pytest.skip(f"reference module unavailable offline: {err}")
@@ -516,7 +507,7 @@ def test_modular_accumulation_ns(ns, name, kwargs, gen, atol):
 
     _tm()
     our_ns = importlib.import_module(f"metrics_amd.{ns}")
-    ref_ns = importlib.import_module(f"torchmetrics.{ns}")
+    ref_ns = ref_module(f"torchmetrics.{ns}")
     our_cls = getattr(our_ns, name, None)
     ref_cls = getattr(ref_ns, name, None)
     if our_cls is None or ref_cls is None:
@@ -596,16 +587,16 @@ def test_modular_accumulation_ns2(ns, name, kwargs, gen, atol):
 
     _tm()
     if name == "PermutationInvariantTraining":
-        import torchmetrics.functional.audio as ref_fa
-
         import metrics_amd.functional.audio as our_fa
+
+        ref_fa = ref_module("torchmetrics.functional.audio")
 
         our_kw = {"metric_func": our_fa.scale_invariant_signal_noise_ratio}
         ref_kw = {"metric_func": ref_fa.scale_invariant_signal_noise_ratio}
     else:
         our_kw = ref_kw = kwargs
     our_ns = importlib.import_module(f"metrics_amd.{ns}")
-    ref_ns = importlib.import_module(f"torchmetrics.{ns}")
+    ref_ns = ref_module(f"torchmetrics.{ns}")
     import warnings
 
     with warnings.catch_warnings():
@@ -653,7 +644,7 @@ def test_modular_accumulation_ns3(ns, name, kwargs, gen, atol):
 
     _tm()
     our_ns = importlib.import_module(f"metrics_amd.{ns}")
-    ref_ns = importlib.import_module(f"torchmetrics.{ns}")
+    ref_ns = ref_module(f"torchmetrics.{ns}")
     our_cls = getattr(our_ns, name, None)
     ref_cls = getattr(ref_ns, name, None)
     if ref_cls is None:
@@ -705,7 +696,7 @@ def test_modular_forward_ns(ns, name, kwargs, gen, atol):
 
     _tm()
     our_ns = importlib.import_module(f"metrics_amd.{ns}")
-    ref_ns = importlib.import_module(f"torchmetrics.{ns}")
+    ref_ns = ref_module(f"torchmetrics.{ns}")
     our_cls = getattr(our_ns, name, None)
     ref_cls = getattr(ref_ns, name, None)
     if ref_cls is None:
@@ -1086,7 +1077,7 @@ def test_modular_accumulation_ns4(ns, name, kwargs, gen, atol):
 
     _tm()
     our_ns = importlib.import_module(f"metrics_amd.{ns}")
-    ref_ns = importlib.import_module(f"torchmetrics.{ns}")
+    ref_ns = ref_module(f"torchmetrics.{ns}")
     our_cls = getattr(our_ns, name, None)
     ref_cls = getattr(ref_ns, name, None)
     if ref_cls is None:
@@ -1133,7 +1124,7 @@ def test_modular_accumulation_ns5(ns, name, kwargs, gen, atol):
 
     _tm()
     our_ns = importlib.import_module(f"metrics_amd.{ns}")
-    ref_ns = importlib.import_module(f"torchmetrics.{ns}")
+    ref_ns = ref_module(f"torchmetrics.{ns}")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         ours, ref = getattr(our_ns, name)(**kwargs), getattr(ref_ns, name)(**kwargs)
@@ -1249,6 +1240,51 @@ def test_ssim_option_differential(opt):
             _cmp(vo, vr, 1e-5)
 
 
+_SIG_NAMESPACES = ["", "classification", "regression", "retrieval", "text", "audio", "image",
+                   "detection", "segmentation", "clustering", "nominal", "aggregation",
+                   "wrappers", "shape", "pairwise", "functional",
+                   "functional.classification", "functional.regression", "functional.retrieval",
+                   "functional.text", "functional.audio", "functional.image",
+                   "functional.detection", "functional.segmentation", "functional.clustering",
+                   "functional.nominal", "functional.pairwise", "functional.shape",
+                   "functional.multimodal"]
+
+
+def _reference_signatures():
+    """{namespace: {callable: [[param, "required" | "value" | "opaque", default], ...]}}
+    of the reference's public callables (runs only while the tape is recorded)."""
+    import importlib
+    import inspect
+
+    from tests.unittests._golden import _to_data
+
+    out = {}
+    for ns in _SIG_NAMESPACES:
+        try:
+            ref_ns = importlib.import_module(f"torchmetrics.{ns}" if ns else "torchmetrics")
+        except Exception:
+            continue
+        sigs = {}
+        for n in getattr(ref_ns, "__all__", []):
+            rc = getattr(ref_ns, n, None)
+            if rc is None or not (inspect.isclass(rc) or callable(rc)):
+                continue
+            try:
+                rsig = inspect.signature(rc.__init__ if inspect.isclass(rc) else rc)
+            except (ValueError, TypeError):
+                continue
+            params = []
+            for pname, rp in rsig.parameters.items():
+                if rp.default is inspect.Parameter.empty:
+                    params.append([pname, "required", None])
+                    continue
+                ok, data = _to_data(rp.default)
+                params.append([pname, "value", data] if ok else [pname, "opaque", repr(rp.default)])
+            sigs[n] = params
+        out[ns] = sigs
+    return out
+
+
 def test_constructor_signature_parity():
     """Every shared public callable accepts at least the reference's named
     parameters (introspection parity: help()/IDE/keyword-call compatible)."""
@@ -1256,43 +1292,37 @@ def test_constructor_signature_parity():
     import inspect
     import warnings
 
-    tm = _tm()
-    namespaces = ["", "classification", "regression", "retrieval", "text", "audio", "image",
-                  "detection", "segmentation", "clustering", "nominal", "aggregation",
-                  "wrappers", "shape", "pairwise", "functional",
-                  "functional.classification", "functional.regression", "functional.retrieval",
-                  "functional.text", "functional.audio", "functional.image",
-                  "functional.detection", "functional.segmentation", "functional.clustering",
-                  "functional.nominal", "functional.pairwise", "functional.shape",
-                  "functional.multimodal"]
+    ref_sigs = ref_value("public signatures", _reference_signatures)
+    # every recorded default is plain data, so each one is compared by value
+    assert not [(ns, n, p) for ns, sigs in ref_sigs.items() for n, ps in sigs.items() for p in ps if p[1] == "opaque"]
     mismatches = []
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        for ns in namespaces:
+        for ns in _SIG_NAMESPACES:
+            if ns not in ref_sigs:
+                continue
             try:
                 our_ns = importlib.import_module(f"metrics_amd.{ns}") if ns else ma
-                ref_ns = importlib.import_module(f"torchmetrics.{ns}") if ns else tm
             except Exception:
                 continue
-            for n in getattr(ref_ns, "__all__", []):
-                rc, oc = getattr(ref_ns, n, None), getattr(our_ns, n, None)
-                if rc is None or oc is None or not (inspect.isclass(rc) or callable(rc)):
+            for n, rparams in ref_sigs[ns].items():
+                oc = getattr(our_ns, n, None)
+                if oc is None:
                     continue
                 try:
-                    rsig = inspect.signature(rc.__init__ if inspect.isclass(rc) else rc)
                     osig = inspect.signature(oc.__init__ if inspect.isclass(oc) else oc)
                 except (ValueError, TypeError):
                     continue
-                miss = [p for p in rsig.parameters
+                miss = [p for p, _, _ in rparams
                         if p not in ("self", "kwargs", "args") and p not in osig.parameters]
                 if miss:
                     mismatches.append((ns or "top", n, miss))
-                for pname, rp in rsig.parameters.items():
+                for pname, kind, rd in rparams:
                     if pname in ("self", "kwargs", "args") or pname not in osig.parameters:
                         continue
-                    rd, od = rp.default, osig.parameters[pname].default
-                    if rd is inspect.Parameter.empty or od is inspect.Parameter.empty:
-                        if (rd is inspect.Parameter.empty) != (od is inspect.Parameter.empty):
+                    od = osig.parameters[pname].default
+                    if kind == "required" or od is inspect.Parameter.empty:
+                        if (kind == "required") != (od is inspect.Parameter.empty):
                             mismatches.append((ns or "top", n, pname, "required-ness", repr(rd), repr(od)))
                         continue
                     eq = rd == od

@@ -3,31 +3,26 @@
 A checkpoint written by the reference must load into our metric and vice
 versa: same keys (prefix + state name), same shapes/dtypes, same semantics
 after restore.
+
+The reference side is replayed from the golden tapes under
+tests/golden/reference/ (see tests/unittests/_golden.py): its state dicts and
+computed values are the recorded ones. What the reference computed from OUR
+checkpoint was recorded too, so test_our_checkpoint_loads_into_reference pins
+our compute() to that record; that our keys, shapes and dtypes are the ones a
+strict load accepts is what test_state_dict_keys_match_reference asserts.
 """
 from __future__ import annotations
 
 import io
-import os
-import sys
 
-import pytest
 import torch
 
-_REF = "/root/reference/src"
-HAVE_REF = os.path.isdir(_REF)
-pytestmark = pytest.mark.skipif(not HAVE_REF, reason="reference tree not available")
-
-if HAVE_REF:
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "tools", "refbench"))
-    sys.path.insert(0, _REF)
-
 import metrics_amd as ma
+from tests.unittests._golden import ref_module
 
 
 def _tm():
-    import torchmetrics as tm
-
-    return tm
+    return ref_module("torchmetrics")
 
 
 def _roundtrip(state_dict):

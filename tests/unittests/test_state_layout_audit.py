@@ -8,24 +8,16 @@ implementations for the whole surface, not just the hand-picked five in
 test_state_dict_compat.py.
 
 Known deliberate deviations are listed with reasons.
+
+The reference's layouts are replayed from the golden tape under
+tests/golden/reference/ (see tests/unittests/_golden.py).
 """
 from __future__ import annotations
 
-import os
-import sys
-
-import pytest
 import torch
 
-_REF = "/root/reference/src"
-HAVE_REF = os.path.isdir(_REF)
-pytestmark = pytest.mark.skipif(not HAVE_REF, reason="reference tree not available")
-
-if HAVE_REF:
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "tools", "refbench"))
-    sys.path.insert(0, _REF)
-
 import metrics_amd as ma
+from tests.unittests._golden import ref_value
 
 # argument guesses tried in order until one constructs BOTH classes
 _ARG_GUESSES = (
@@ -72,14 +64,38 @@ def _instantiate(cls):
     return None, None
 
 
-def test_state_layout_matches_reference():
+def _reference_layouts():
+    """{top-level name: None | [constructor kwargs, {state: ["tensor", shape, dtype] | ["list"]}]}
+    for everything the reference exports (runs only while the tape is recorded)."""
+    import warnings
+
     import torchmetrics as tm
 
-    common = sorted(set(dir(ma)) & set(dir(tm)))
+    out = {}
+    for name in dir(tm):
+        ref_cls = getattr(tm, name)
+        out[name] = None
+        if not isinstance(ref_cls, type):
+            continue
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ref, kw = _instantiate(ref_cls)
+        if ref is None or not hasattr(ref, "_defaults"):
+            continue
+        out[name] = [kw, {
+            k: ["tensor", tuple(d.shape), str(d.dtype)] if isinstance(d, torch.Tensor) else ["list"]
+            for k, d in ref._defaults.items()
+        }]
+    return out
+
+
+def test_state_layout_matches_reference():
+    ref_layouts = ref_value("state layouts", _reference_layouts)
+
+    common = sorted(set(dir(ma)) & set(ref_layouts))
     checked, mismatches, skipped = [], [], []
     for name in common:
         ours_cls = getattr(ma, name)
-        ref_cls = getattr(tm, name)
         if not (isinstance(ours_cls, type) and issubclass(ours_cls, ma.Metric)):
             continue
         if name in _KNOWN_DEVIATIONS:
@@ -89,20 +105,20 @@ def test_state_layout_matches_reference():
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             ours, kw1 = _instantiate(ours_cls)
-            ref, kw2 = _instantiate(ref_cls)
-        if ours is None or ref is None or kw1 != kw2:
+        kw2, ref_defaults = ref_layouts[name] or (None, None)
+        if ours is None or ref_defaults is None or kw1 != kw2:
             skipped.append(name)
             continue
-        k1, k2 = set(ours._defaults), set(ref._defaults)
+        k1, k2 = set(ours._defaults), set(ref_defaults)
         if k1 != k2:
             mismatches.append((name, sorted(k1), sorted(k2)))
             continue
         for k in k1:
-            d1, d2 = ours._defaults[k], ref._defaults[k]
-            if isinstance(d1, torch.Tensor) != isinstance(d2, torch.Tensor):
-                mismatches.append((name, k, type(d1), type(d2)))
-            elif isinstance(d1, torch.Tensor) and (d1.shape != d2.shape or d1.dtype != d2.dtype):
-                mismatches.append((name, k, (d1.shape, d1.dtype), (d2.shape, d2.dtype)))
+            d1, d2 = ours._defaults[k], ref_defaults[k]
+            if isinstance(d1, torch.Tensor) != (d2[0] == "tensor"):
+                mismatches.append((name, k, type(d1), d2[0]))
+            elif isinstance(d1, torch.Tensor) and (tuple(d1.shape) != tuple(d2[1]) or str(d1.dtype) != d2[2]):
+                mismatches.append((name, k, (d1.shape, d1.dtype), (d2[1], d2[2])))
         checked.append(name)
     assert len(checked) >= 60, f"audit only covered {len(checked)} classes (skipped: {skipped[:20]})"
     assert not mismatches, mismatches
