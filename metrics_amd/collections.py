@@ -49,6 +49,14 @@ class _FusedMulticlassUpdatePlan:
         self.exact = exact
         self.curve = curve
         self.leaders = tuple(m for m in (stat, confmat, exact, curve) if m is not None)
+        # one-pass step (logits read once); METRICS_AMD_ONEPASS=0 keeps the
+        # stat + curve-hist + apply kernel sequence, 2 lifts the shape gate
+        from metrics_amd.ops import _hip
+
+        mode = _hip.onepass_mode()
+        self.onepass = curve is not None and mode != 0
+        self.onepass_force = mode == 2
+        self.onepass_steps = 0
 
     @staticmethod
     def build(collection) -> "Optional[_FusedMulticlassUpdatePlan]":
@@ -118,6 +126,17 @@ class _FusedMulticlassUpdatePlan:
                 rbuf = torch.empty(2, preds.shape[0], dtype=torch.float32, device=preds.device)
                 curve.__dict__["_hip_rowstats_buf"] = rbuf
             ebuf = _hip._epoch_buf(preds.device, curve)
+            # one native call for the whole step, logits read once; False ->
+            # shape not covered, nothing launched, keep the kernel sequence below
+            if self.onepass and _hip.mc_onepass_update(
+                preds, target, stat.num_classes, stat.ignore_index,
+                (scratch, stat.tp, stat.fp, stat.tn, stat.fn),
+                self.confmat.confmat if self.confmat is not None else None,
+                (self.exact.correct, self.exact.total) if self.exact is not None else None,
+                rbuf, ebuf, curve, self.onepass_force,
+            ):
+                self.onepass_steps += 1
+                return self.leaders
             rowstats = (rbuf[0], rbuf[1], ebuf)
         elif curve is not None:
             curve = None  # label preds: curve can't ride the fused pass

@@ -27,6 +27,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "curve_common.h"
+
 #define WAVE 64
 #define CHECK(x)                                                                                   \
     do {                                                                                           \
@@ -36,10 +38,6 @@
 
 typedef long long ll;
 
-__device__ __forceinline__ float bf16_to_f32(unsigned short u) {
-    unsigned int v = ((unsigned int)u) << 16;
-    return __uint_as_float(v);
-}
 
 // ---------------------------------------------------------------------------
 // K1a: fused row-argmax + multiclass stat scores from logits (B, C)
@@ -478,27 +476,7 @@ __global__ void __launch_bounds__(256) k_multilabel_stat(
 // hist layout (T+1, 2): [bucket][target]. The (T,2,2) confmat state is the
 // suffix-sum, computed by k_curve_suffix below.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int bucket_of(float p, const float* __restrict__ thr, int T) {
-    int lo = 0, hi = T;  // count of thresholds <= p
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (thr[mid] <= p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// For (near-)uniform threshold grids (the linspace default): O(1) guess from
-// the spacing, then an EXACT +-1 fixup against the actual threshold values —
-// bit-identical to the binary search at ~2 LDS reads instead of log2(T).
-__device__ __forceinline__ int bucket_of_uniform(float p, const float* __restrict__ thr, int T,
-                                                 float t0, float inv_step) {
-    int j = (int)floorf((p - t0) * inv_step) + 1;
-    j = j < 0 ? 0 : (j > T ? T : j);
-    while (j < T && thr[j] <= p) j++;
-    while (j > 0 && thr[j - 1] > p) j--;
-    return j;
-}
+// bucket_of / bucket_of_uniform: see curve_common.h
 
 // detect values outside [0,1] (=> inputs are logits, normalize in-kernel).
 // DEVICE-epoch protocol (hipGraph-capturable, no host state): E[1] counts
@@ -649,7 +627,14 @@ __global__ void __launch_bounds__(256) k_multiclass_curve_hist(
     int uniform, float t0, float inv_step, int c_chunk,
     int norm_kind /*0 none, 1 softmax (rowstats), 2 sigmoid*/, const unsigned int* __restrict__ E,
     const float* __restrict__ rowmax, const float* __restrict__ rowinv,
+    const unsigned long long* __restrict__ n_deferred /* nullable: skip-done mode */,
     unsigned long long* __restrict__ hist /* (C, T+1, 2) */) {
+    // skip-done mode (deferred pass behind k_mc_onepass, csrc/mc_onepass.hip):
+    // the one-pass kernel already binned every row it could decide on its own
+    // and marked it rowinv < 0; when it deferred nothing, every block leaves
+    // here. The value is final (written by the previous kernel on the stream),
+    // so the exit is uniform across the grid.
+    if (n_deferred && *n_deferred == 0ULL) return;
     extern __shared__ float sthr2[];
     for (int b = threadIdx.x; b < T; b += blockDim.x) sthr2[b] = thresholds[b];
     __syncthreads();
@@ -675,6 +660,7 @@ __global__ void __launch_bounds__(256) k_multiclass_curve_hist(
         trow = target[row];
         if (has_ignore && trow == ignore_index) valid = false;
     }
+    if (n_deferred && valid && rowinv[row] < 0.0f) valid = false;  // done in the one-pass kernel
     const int norm = (norm_kind && E && E[0] == E[1] + 1u) ? norm_kind : 0;
     const float rmax = (norm == 1 && valid) ? rowmax[row] : 0.0f;
     const float rinv = (norm == 1 && valid) ? rowinv[row] : 0.0f;
@@ -1549,11 +1535,12 @@ int ma_binary_curve_hist(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
     return (int)hipGetLastError();
 }
 
-int ma_multiclass_curve_hist(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target, ll B,
-                             ll C, uintptr_t thresholds, int T, ll ignore_index, int has_ignore,
-                             int mode, int uniform, float t0, float inv_step, int norm_kind,
-                             uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv, int variant,
-                             int c_chunk_override, int stats_ready, uintptr_t hist) {
+static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target, ll B,
+                              ll C, uintptr_t thresholds, int T, ll ignore_index, int has_ignore,
+                              int mode, int uniform, float t0, float inv_step, int norm_kind,
+                              uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv, int variant,
+                              int c_chunk_override, int stats_ready, uintptr_t n_deferred,
+                              uintptr_t hist) {
     hipStream_t s = (hipStream_t)stream;
     size_t shmem = (size_t)T * sizeof(float);
     if (shmem > 160 * 1024) return -100;
@@ -1627,14 +1614,40 @@ int ma_multiclass_curve_hist(uintptr_t stream, uintptr_t probs, int dtype, uintp
             (const float*)probs, (const ll*)target, B, C, (const float*)thresholds, T, ignore_index,
             has_ignore, mode, uniform, t0, inv_step, c_chunk, norm_kind,
             (const unsigned int*)flag, (const float*)rowmax, (const float*)rowinv,
-            (unsigned long long*)hist);
+            (const unsigned long long*)n_deferred, (unsigned long long*)hist);
     else
         k_multiclass_curve_hist<unsigned short, true><<<grid, 256, shmem, s>>>(
             (const unsigned short*)probs, (const ll*)target, B, C, (const float*)thresholds, T,
             ignore_index, has_ignore, mode, uniform, t0, inv_step, c_chunk, norm_kind,
             (const unsigned int*)flag, (const float*)rowmax, (const float*)rowinv,
-            (unsigned long long*)hist);
+            (const unsigned long long*)n_deferred, (unsigned long long*)hist);
     return (int)hipGetLastError();
+}
+
+int ma_multiclass_curve_hist(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target, ll B,
+                             ll C, uintptr_t thresholds, int T, ll ignore_index, int has_ignore,
+                             int mode, int uniform, float t0, float inv_step, int norm_kind,
+                             uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv, int variant,
+                             int c_chunk_override, int stats_ready, uintptr_t hist) {
+    return mc_curve_hist_impl(stream, probs, dtype, target, B, C, thresholds, T, ignore_index,
+                              has_ignore, mode, uniform, t0, inv_step, norm_kind, flag, rowmax,
+                              rowinv, variant, c_chunk_override, stats_ready, 0, hist);
+}
+
+// Deferred pass behind the one-pass update (csrc/mc_onepass.hip): the
+// ballot-merge kernel in skip-done mode. Exits at once when the one-pass
+// kernel deferred no row; otherwise bins exactly the rows it left (rowinv > 0),
+// softmaxed iff the epoch flag is set.
+int ma_mc_curve_hist_deferred(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target,
+                              ll B, ll C, uintptr_t thresholds, int T, ll ignore_index,
+                              int has_ignore, int uniform, float t0, float inv_step,
+                              uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv,
+                              uintptr_t n_deferred, uintptr_t hist) {
+    if (!n_deferred) return -102;
+    return mc_curve_hist_impl(stream, probs, dtype, target, B, C, thresholds, T, ignore_index,
+                              has_ignore, /*mode=*/0, uniform, t0, inv_step, /*norm_kind=*/1, flag,
+                              rowmax, rowinv, /*variant=*/0, /*c_chunk_override=*/0,
+                              /*stats_ready=*/1, n_deferred, hist);
 }
 
 int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int transposed,

@@ -1,0 +1,416 @@
+// One-pass update for the fused multiclass collection plan (gfx950).
+//
+// The two-kernel path reads the (B, C) logits twice: k_mc_stat_logits (argmax,
+// tp/fp/fn/confmat, online-softmax row stats, out-of-range epoch flag) and
+// then k_multiclass_curve_hist, which has to wait for a kernel boundary
+// because "softmax iff ANY element of the batch lies outside [0,1]" is a
+// batch-global decision. Here a wave owns a row and keeps the whole row in
+// registers (16 B per lane per vector, NV vectors per lane), so the row is
+// read from HBM once:
+//
+//  phase A  exactly k_mc_stat_logits: same fold order, same shuffle tree, so
+//           rowmax/rowinv are bit-identical to the two-kernel path.
+//  phase B  CERTAINTY RULE: if this row itself holds an element outside
+//           [0,1], the batch-global answer is already known to be "softmax",
+//           and the row is binned from registers right away. A row with every
+//           element in [0,1] cannot know the answer; it is DEFERRED to the
+//           skip-done mode of k_multiclass_curve_hist (kernels.hip), which
+//           runs behind this kernel and exits at once when n_deferred == 0.
+//           There is no grid-wide barrier anywhere.
+//
+// COMPLEMENT IDENTITY: after softmax almost every element of a row falls into
+// one bucket b0 = bucket_of(+0.0f). Those elements issue no atomic at all.
+// Per class the kernel counts P[c] (binned rows whose target is c) and
+// N1[c]/N0[c] (elements binned OUTSIDE b0, by label); the epilogue adds
+//     hist[c][b0][1] += P[c] - N1[c]
+//     hist[c][b0][0] += (n_binned - P[c]) - N0[c]
+// which is an exact integer identity (class total minus the rest), so the
+// histogram equals the two-kernel result bit for bit.
+//
+// A done row (binned or ignored) is marked rowinv[row] = -rinv; a true rinv is
+// always > 0, so the sign is free.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "curve_common.h"
+
+#define WAVE 64
+
+typedef long long ll;
+typedef unsigned long long ull;
+
+// curve scratch layout (u64): [P: C][N1: C][N0: NCOPY x C][n_binned][n_deferred]
+// N0[c] takes ~150 increments per class and step at the bench shape; on one
+// address they serialise (measured: 10 us of the kernel). NCOPY copies, picked
+// by block index (consecutive blocks land on different XCDs), spread them; the
+// epilogue sums the copies.
+#define ONEPASS_NCOPY 8
+#define ONEPASS_CS_WORDS(C) ((2 + ONEPASS_NCOPY) * (C) + 2)
+template <bool IS_BF16, int NV>
+__global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_onepass(
+    const uint4* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
+    int has_ignore, ull* __restrict__ tp, ull* __restrict__ fp, ull* __restrict__ fn,
+    ull* __restrict__ confmat, ull* __restrict__ valid_count, float* __restrict__ rowmax,
+    float* __restrict__ rowinv, unsigned int* __restrict__ E,
+    const float* __restrict__ thresholds, int T, int uniform, float t0, float inv_step,
+    ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cs /* ONEPASS_CS_WORDS(C) */) {
+    constexpr int EPV = IS_BF16 ? 8 : 4;  // elements per 16-byte vector
+    extern __shared__ float sthr[];
+    __shared__ unsigned int block_valid, blk_outside, blk_binned, blk_deferred;
+
+    const int lane = threadIdx.x & (WAVE - 1);
+    // wave-uniform by construction; tell the compiler, so the row index and
+    // everything derived from it live in scalar registers
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int waves_per_block = blockDim.x / WAVE;
+    const ll row_stride = (ll)gridDim.x * waves_per_block;
+    const int nvec = (int)(C / EPV);  // C <= 4096 here: 32-bit class indices
+    const unsigned int cur_epoch = E[1] + 1u;
+    ull* __restrict__ cP = cs;
+    ull* __restrict__ cN1 = cs + C;
+    ull* __restrict__ cN0 = cs + (2 + (blockIdx.x & (ONEPASS_NCOPY - 1))) * C;
+    unsigned int outside = 0;
+    unsigned int my_valid = 0, my_binned = 0, my_deferred = 0;
+
+    auto unpack = [](const uint4& u, float* f) {
+        if (IS_BF16) {
+            f[0] = bf16_to_f32((unsigned short)(u.x & 0xffffu)); f[1] = bf16_to_f32((unsigned short)(u.x >> 16));
+            f[2] = bf16_to_f32((unsigned short)(u.y & 0xffffu)); f[3] = bf16_to_f32((unsigned short)(u.y >> 16));
+            f[4] = bf16_to_f32((unsigned short)(u.z & 0xffffu)); f[5] = bf16_to_f32((unsigned short)(u.z >> 16));
+            f[6] = bf16_to_f32((unsigned short)(u.w & 0xffffu)); f[7] = bf16_to_f32((unsigned short)(u.w >> 16));
+        } else {
+            f[0] = __uint_as_float(u.x); f[1] = __uint_as_float(u.y);
+            f[2] = __uint_as_float(u.z); f[3] = __uint_as_float(u.w);
+        }
+    };
+
+    // the whole row, packed, in registers: vector k of this lane is pv[lane + 64*k]
+    uint4 r[NV];
+    auto load_row = [&](ll row) {
+        const uint4* pv = preds + row * (ll)nvec;
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            const int v = lane + k * WAVE;
+            r[k] = v < nvec ? pv[v] : make_uint4(0u, 0u, 0u, 0u);
+        }
+    };
+    // the first row's loads are in flight while the block stages the thresholds
+    ll row = (ll)blockIdx.x * waves_per_block + wave_in_block;
+    if (row < B) load_row(row);
+    for (int b = threadIdx.x; b < T; b += blockDim.x) sthr[b] = thresholds[b];
+    if (threadIdx.x == 0) { block_valid = 0; blk_outside = 0; blk_binned = 0; blk_deferred = 0; }
+    __syncthreads();
+    const int b0 = bucket_of(0.0f, sthr, T);
+    const float hi0 = b0 < T ? sthr[b0] : INFINITY;  // bucket b0 is [thr[b0-1], thr[b0])
+
+    while (row < B) {
+        const ll t = target[row];
+
+        // ---- phase A: k_mc_stat_logits, same fold and tie-break ----
+        float best = -INFINITY;
+        int best_idx = 0x7fffffff;
+        float sm_m = -3.4e38f, sm_s = 0.0f;  // online softmax (max, sumexp)
+        unsigned int row_out = 0;
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            const int v = lane + k * WAVE;
+            if (v < nvec) {
+                float f[EPV];
+                unpack(r[k], f);
+                float m8 = f[0];
+#pragma unroll
+                for (int i = 1; i < EPV; i++) m8 = fmaxf(m8, f[i]);
+                float s8 = 0.0f;
+#pragma unroll
+                for (int i = 0; i < EPV; i++) {
+                    row_out |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
+                    s8 += __expf(f[i] - m8);
+                }
+                if (m8 > sm_m) { sm_s = sm_s * __expf(sm_m - m8) + s8; sm_m = m8; }
+                else { sm_s += s8 * __expf(m8 - sm_m); }
+                const int c = v * EPV;
+#pragma unroll
+                for (int i = 0; i < EPV; i++) {
+                    if (f[i] > best || (f[i] == best && c + i < best_idx)) { best = f[i]; best_idx = c + i; }
+                }
+            }
+        }
+        outside |= row_out;
+        for (int off = WAVE / 2; off > 0; off >>= 1) {
+            float om = __shfl_down(sm_m, off);
+            float os = __shfl_down(sm_s, off);
+            if (om > sm_m) { sm_s = sm_s * __expf(sm_m - om) + os; sm_m = om; }
+            else { sm_s += os * __expf(om - sm_m); }
+        }
+        for (int off = WAVE / 2; off > 0; off >>= 1) {
+            float ov = __shfl_down(best, off);
+            int oi = __shfl_down(best_idx, off);
+            if (ov > best || (ov == best && oi < best_idx)) { best = ov; best_idx = oi; }
+        }
+        // lane 0 holds the row's (max, sumexp); every lane needs them for phase B
+        const float rmax = __shfl(sm_m, 0);
+        const float rinv = __shfl(1.0f / sm_s, 0);
+        const bool ignored = has_ignore && t == ignore_index;
+        const bool certain = __ballot(row_out != 0u) != 0ULL;  // this row alone proves "softmax"
+        const bool bin_now = certain && !ignored;
+        if (lane == 0) {
+            const ll p = best_idx;
+            // bounds guard: bad labels with validate_args=False must not corrupt memory
+            if (!ignored && t >= 0 && t < C && p >= 0 && p < C) {
+                my_valid++;
+                if (p == t) {
+                    atomicAdd(&tp[t], 1ULL);
+                } else {
+                    atomicAdd(&fp[p], 1ULL);
+                    atomicAdd(&fn[t], 1ULL);
+                }
+                if (confmat) atomicAdd(&confmat[t * C + p], 1ULL);
+            }
+            rowmax[row] = rmax;
+            rowinv[row] = (bin_now || ignored) ? -rinv : rinv;
+            if (bin_now) {
+                my_binned++;
+                if (t >= 0 && t < C) atomicAdd(&cP[t], 1ULL);
+            } else if (!ignored) {
+                my_deferred++;
+            }
+        }
+
+        // ---- phase B: bin from registers; bucket b0 is filled by the epilogue ----
+        if (bin_now) {
+            // out-of-range targets bin with every label 0, like the two-kernel path
+            const int tc = (t >= 0 && t < C) ? (int)t : -1;
+            auto bin_one = [&](float x, int c) {
+                const float p = expf(x - rmax) * rinv;
+                const int j = uniform ? bucket_of_uniform(p, sthr, T, t0, inv_step)
+                                      : bucket_of(p, sthr, T);
+                if (j != b0) {
+                    const int label = (tc == c) ? 1 : 0;
+                    atomicAdd(&hist[(ull)c * (T + 1) * 2 + j * 2 + label], 1ULL);
+                    atomicAdd(label ? &cN1[c] : &cN0[c], 1ULL);
+                }
+            };
+            // EXACT pre-filter in the logit domain. p = expf(d) * rinv with
+            // d = x - rmax; bucket(p) == b0 <=> thr[b0-1] <= p < thr[b0].
+            // The left half always holds (thr[b0-1] <= 0 <= p). For the right
+            // half: d < log(hi0 * sumexp) - 1e-3 gives exp(d) * rinv <
+            // hi0 * e^-1e-3, and the rounding of logf, expf and the product
+            // (a few 1e-7 relative, 1e-5 absolute on the log) is far inside
+            // the 1e-3 margin — such an element is certainly in b0 and costs
+            // a subtract and a compare. Everything else, NaN included (the
+            // compare is false), goes through expf and bucket_of unchanged.
+            const float dcut = logf(hi0 * __shfl(sm_s, 0)) - 1e-3f;
+            ull todo = 0;  // bit k*EPV+i: element i of vector k needs the full path
+#pragma unroll
+            for (int k = 0; k < NV; k++) {
+                if (lane + k * WAVE < nvec) {
+                    float f[EPV];
+                    unpack(r[k], f);
+#pragma unroll
+                    for (int i = 0; i < EPV; i++)
+                        todo |= (f[i] - rmax < dcut) ? 0ULL : (1ULL << (k * EPV + i));
+                }
+            }
+            // compacted: every lane pops one pending element per round, so a
+            // row costs max-over-lanes(popcount) rounds, not EPV*NV
+            while (__ballot(todo != 0ULL) != 0ULL) {
+                if (todo != 0ULL) {
+                    const int e = __ffsll(todo) - 1;
+                    todo &= todo - 1ULL;
+                    const int wi = IS_BF16 ? (e >> 1) : e;  // 32-bit word of the row slice
+                    unsigned int w = r[0].x;
+#pragma unroll
+                    for (int q = 1; q < 4 * NV; q++) {
+                        const unsigned int cand = (q & 3) == 0 ? r[q >> 2].x
+                                                : (q & 3) == 1 ? r[q >> 2].y
+                                                : (q & 3) == 2 ? r[q >> 2].z
+                                                               : r[q >> 2].w;
+                        w = (wi == q) ? cand : w;
+                    }
+                    const float x = IS_BF16 ? __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16))
+                                            : __uint_as_float(w);
+                    const int k = e / EPV, i = e % EPV;
+                    bin_one(x, (lane + k * WAVE) * EPV + i);
+                }
+            }
+        }
+        row += row_stride;
+        if (row < B) load_row(row);  // r is dead here: same registers
+    }
+    // one atomic per block for each scalar counter
+    if (my_valid) atomicAdd(&block_valid, my_valid);
+    if (my_binned) atomicAdd(&blk_binned, my_binned);
+    if (my_deferred) atomicAdd(&blk_deferred, my_deferred);
+    for (int off = WAVE / 2; off > 0; off >>= 1) outside |= __shfl_down(outside, off);
+    if (lane == 0 && outside) atomicOr(&blk_outside, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (block_valid) atomicAdd(valid_count, (ull)block_valid);
+        if (blk_binned) atomicAdd(&cs[(2 + ONEPASS_NCOPY) * C], (ull)blk_binned);
+        if (blk_deferred) atomicAdd(&cs[(2 + ONEPASS_NCOPY) * C + 1], (ull)blk_deferred);
+        if (blk_outside && E[0] != cur_epoch) atomicMax(&E[0], cur_epoch);
+    }
+}
+
+// Epilogue of the one-pass step: k_apply_stat_exact (stat deltas, optional
+// exact-match) plus the complement fill of bucket b0, in ONE single-block
+// launch. Consumes and re-zeroes both scratches in flight (each slot is read
+// and zeroed by the same thread) and closes the device epoch as its last act.
+__global__ void __launch_bounds__(1024) k_onepass_apply(
+    ull* __restrict__ scratch /* 3*C + 1 */, ll C, ll B, ll* __restrict__ tp, ll* __restrict__ fp,
+    ll* __restrict__ tn, ll* __restrict__ fn, ll* __restrict__ correct /* nullable */,
+    ll* __restrict__ total, unsigned int* __restrict__ E, ull* __restrict__ cs /* ONEPASS_CS_WORDS(C) */,
+    const float* __restrict__ thresholds, int T, ull* __restrict__ hist /* (C, T+1, 2) */) {
+    __shared__ ull part[1024];
+    __shared__ ull valid_s, binned_s;
+    extern __shared__ float sthr_a[];  // a global-memory binary search is ~8 dependent misses
+    for (int b = threadIdx.x; b < T; b += blockDim.x) sthr_a[b] = thresholds[b];
+    if (threadIdx.x == 0) { valid_s = scratch[3 * C]; binned_s = cs[(2 + ONEPASS_NCOPY) * C]; }
+    __syncthreads();
+    const ll valid = (ll)valid_s;
+    const ll binned = (ll)binned_s;
+    if (threadIdx.x == 0) { scratch[3 * C] = 0; cs[(2 + ONEPASS_NCOPY) * C] = 0; cs[(2 + ONEPASS_NCOPY) * C + 1] = 0; }
+    const int b0 = bucket_of(0.0f, sthr_a, T);
+    ull acc = 0;
+    for (ll i = threadIdx.x; i < C; i += blockDim.x) {
+        const ll dtp = (ll)scratch[i];
+        const ll dfp = (ll)scratch[C + i];
+        const ll dfn = (ll)scratch[2 * C + i];
+        scratch[i] = 0;
+        scratch[C + i] = 0;
+        scratch[2 * C + i] = 0;
+        acc += (ull)dtp;
+        tp[i] += dtp;
+        fp[i] += dfp;
+        fn[i] += dfn;
+        tn[i] += valid - dtp - dfp - dfn;
+        if (binned) {  // no row binned => the three counters are already zero
+            const ll P = (ll)cs[i];
+            const ll N1 = (ll)cs[C + i];
+            ll N0 = 0;
+#pragma unroll
+            for (int q = 0; q < ONEPASS_NCOPY; q++) {
+                N0 += (ll)cs[(2 + q) * C + i];
+                cs[(2 + q) * C + i] = 0;
+            }
+            cs[i] = 0;
+            cs[C + i] = 0;
+            ll* h = (ll*)hist + ((ull)i * (T + 1) + b0) * 2;
+            h[1] += P - N1;
+            h[0] += (binned - P) - N0;
+        }
+    }
+    if (correct) {
+        part[threadIdx.x] = acc;
+        __syncthreads();
+        for (int off = 512; off > 0; off >>= 1) {
+            if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            correct[0] += (ll)part[0] + (B - valid);
+            total[0] += B;
+        }
+    }
+    if (threadIdx.x == 0) E[1] += 1u;
+}
+
+extern "C" {
+
+// kernels.hip
+int ma_mc_curve_hist_deferred(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target,
+                              ll B, ll C, uintptr_t thresholds, int T, ll ignore_index,
+                              int has_ignore, int uniform, float t0, float inv_step,
+                              uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv,
+                              uintptr_t n_deferred, uintptr_t hist);
+
+// NV (16-byte vectors per lane) the one-pass kernel would use, 0 = unsupported
+// shape (caller keeps the two-kernel path). NV in {1,2,4,8}; NV <= 2 (bf16
+// C <= 1024, fp32 C <= 512) compiles to <= 64 VGPRs = 8 waves per SIMD, NV=4
+// to 5-7 and NV=8 to 3-4 waves, none with scratch (profiles/README.md).
+int ma_mc_onepass_nv(int dtype /*0=f32 1=bf16*/, ll C, int T) {
+    if (C <= 128 || T < 1 || (size_t)T * sizeof(float) > 48 * 1024) return 0;
+    const int epv = dtype == 1 ? 8 : 4;
+    if (dtype != 0 && dtype != 1) return 0;
+    if (C % epv) return 0;
+    const ll per_lane = (C / epv + WAVE - 1) / WAVE;
+    if (per_lane > 8) return 0;
+    int nv = 1;
+    while (nv < per_lane) nv *= 2;
+    return nv;
+}
+
+// u64 words of the curve scratch for C classes
+int ma_mc_onepass_scratch_words(ll C) { return (int)ONEPASS_CS_WORDS(C); }
+
+#define ONEPASS_LAUNCH(BF, NV_)                                                                   \
+    k_mc_onepass<BF, NV_><<<grid, 256, shmem, s>>>(                                               \
+        (const uint4*)preds, (const ll*)target, B, C, ignore_index, has_ignore, sc, sc + C,       \
+        sc + 2 * C, (ull*)confmat, sc + 3 * C, (float*)rowmax, (float*)rowinv,                    \
+        (unsigned int*)epoch_buf, (const float*)thresholds, T, uniform, t0, inv_step, (ull*)hist, \
+        (ull*)cscratch)
+
+// The whole fused-collection step on one stream: one-pass kernel, deferred
+// histogram pass (early exit when nothing was deferred), epilogue.
+// scratch = stat scratch [tp|fp|fn|valid] (3*C+1 u64), cscratch = curve
+// scratch [P|N1|N0 copies|n_binned|n_deferred] (ma_mc_onepass_scratch_words(C)
+// u64); both zero on entry and
+// zero again after the epilogue. correct/total may be 0 (no exact-match leader).
+int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t target, ll B,
+                         ll C, ll ignore_index, int has_ignore, uintptr_t scratch,
+                         uintptr_t confmat, uintptr_t tp, uintptr_t fp, uintptr_t tn, uintptr_t fn,
+                         uintptr_t correct, uintptr_t total, uintptr_t rowmax, uintptr_t rowinv,
+                         uintptr_t epoch_buf, uintptr_t thresholds, int T, int uniform, float t0,
+                         float inv_step, uintptr_t hist, uintptr_t cscratch) {
+    hipStream_t s = (hipStream_t)stream;
+    const int nv = ma_mc_onepass_nv(dtype, C, T);
+    if (nv == 0 || (preds & 15) || !scratch || !cscratch || !hist || !rowmax || !rowinv ||
+        !epoch_buf || !thresholds)
+        return -103;
+    if ((B + 255) / 256 > 65535) return -101;  // the deferred pass's grid.y limit
+    if (B > 0) {
+        ull* sc = (ull*)scratch;
+        const size_t shmem = (size_t)T * sizeof(float);
+        // one row per wave and pass, 4 waves per block. Measured at B=8192
+        // C=1000 (sweep knob MA_ONEPASS_GRID): 2048 blocks — every row
+        // resident at once — run the load, fold and binning phases chip-wide
+        // in lock step (53 us/step); with 512-1024 blocks each wave takes
+        // several rows, the waves drift apart and the phases overlap (45 us)
+        static int gcap = 0;
+        if (gcap == 0) {
+            const char* e = getenv("MA_ONEPASS_GRID");
+            gcap = e ? atoi(e) : 1024;
+            if (gcap < 64) gcap = 64;
+        }
+        ll g = (B + 3) / 4;
+        if (g > gcap) g = gcap;
+        const int grid = (int)g;
+        if (dtype == 1) {
+            if (nv == 1) ONEPASS_LAUNCH(true, 1);
+            else if (nv == 2) ONEPASS_LAUNCH(true, 2);
+            else if (nv == 4) ONEPASS_LAUNCH(true, 4);
+            else ONEPASS_LAUNCH(true, 8);
+        } else {
+            if (nv == 1) ONEPASS_LAUNCH(false, 1);
+            else if (nv == 2) ONEPASS_LAUNCH(false, 2);
+            else if (nv == 4) ONEPASS_LAUNCH(false, 4);
+            else ONEPASS_LAUNCH(false, 8);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        int rc = ma_mc_curve_hist_deferred(stream, preds, dtype, target, B, C, thresholds, T,
+                                           ignore_index, has_ignore, uniform, t0, inv_step,
+                                           epoch_buf, rowmax, rowinv,
+                                           cscratch + (uintptr_t)((2 + ONEPASS_NCOPY) * C + 1) * sizeof(ull), hist);
+        if (rc != 0) return rc;
+    }
+    k_onepass_apply<<<1, 1024, (size_t)T * sizeof(float), s>>>((ull*)scratch, C, B, (ll*)tp, (ll*)fp, (ll*)tn, (ll*)fn,
+                                       (ll*)correct, (ll*)total, (unsigned int*)epoch_buf,
+                                       (ull*)cscratch, (const float*)thresholds, T, (ull*)hist);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

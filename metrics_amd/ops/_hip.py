@@ -59,6 +59,9 @@ _SIGNATURES = {
     "ma_linear_stat_multi": [_U64, _U64, _U64, _U64, _U64, _LL, _I, _U64, _U64],
     "ma_apply_stat_deltas": [_U64, _U64, _LL, _U64, _U64, _U64, _U64, _U64],
     "ma_exact_apply": [_U64, _U64, _LL, _LL, _I, _U64, _U64],
+    "ma_mc_onepass_nv": [_I, _LL, _I],
+    "ma_mc_onepass_scratch_words": [_LL],
+    "ma_mc_onepass_update": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64],
     "ma_apply_stat_exact": [_U64, _U64, _LL, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
     "ma_curve_auc_from_confmat": [_U64, _U64, _I, _LL, _I, _U64, _U64],
     "ma_linear_stat_compute": [_U64, _U64, _U64, _U64, _U64, _LL, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _F, _F, _F, _U64],
@@ -1409,3 +1412,91 @@ def mc_fused_collection_update(
         return _apply_pass
     _apply_pass()
     return None
+
+
+# One-pass fused-collection step (csrc/mc_onepass.hip). METRICS_AMD_ONEPASS:
+#   0  off: the stat + curve-hist + apply kernel sequence, exactly as before
+#      (A/B lever and escape hatch)
+#   1  (default) on where the guard table in profiles/README.md shows a gain:
+#      C >= 5*T. The saving rests on most softmax outputs falling below the
+#      first positive threshold (~1/T on a linspace grid) while a row's mean
+#      probability is 1/C; measured at T=200: C=1000 and 4096 win, C<=512 lose.
+#   2  on for every shape the kernel covers (tests, sweeps)
+# It is read when a collection builds its fused plan.
+ONEPASS_ENV = "METRICS_AMD_ONEPASS"
+_ONEPASS_C_PER_T = 5
+_ONEPASS_NV_CACHE: dict = {}
+
+
+def onepass_mode() -> int:
+    v = os.environ.get(ONEPASS_ENV, "1")
+    return int(v) if v in ("0", "1", "2") else 1
+
+
+def mc_onepass_update(
+    preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int],
+    stat, confmat: Optional[Tensor], exact, rowstats_buf: Tensor, epoch_buf: Tensor, curve,
+    force: bool = False,
+) -> bool:
+    """The whole fused-collection step (stat scores, confusion matrix, exact
+    match, threshold-curve histogram) in ONE native call that reads the logits
+    once: one-pass kernel + deferred histogram pass + epilogue, all enqueued on
+    the current stream. No allocation in steady state and no host sync, so it
+    is hipGraph-capturable.
+
+    Returns False without launching anything when the shape is not covered
+    (C <= 128, C not a multiple of the vector width, row too long for the
+    register layout, unaligned storage) or, unless ``force``, lies below the
+    C >= 5*T gate: the caller keeps the two-kernel path.
+    ``stat``/``exact`` as in :func:`mc_fused_collection_update`;
+    ``rowstats_buf`` is the (2, >=B) float32 rowmax/rowinv buffer, ``epoch_buf``
+    the curve leader's device-epoch buffer, ``curve`` the curve leader (owns the histogram and the curve scratch).
+    """
+    lib = _lib()
+    C = num_classes
+    thr = curve.thresholds.contiguous().float()
+    T = thr.numel()
+    if not force and C < _ONEPASS_C_PER_T * T:
+        return False
+    preds = _to_supported(preds).contiguous()
+    dt = _dtype_code(preds)
+    key = (dt, C, T)
+    hit = _ONEPASS_NV_CACHE.get(key)
+    if hit is None:
+        hit = _ONEPASS_NV_CACHE[key] = (lib.ma_mc_onepass_nv(dt, C, T), lib.ma_mc_onepass_scratch_words(C))
+    nv, cs_words = hit
+    if nv == 0 or preds.data_ptr() % 16:
+        return False
+    target = target.contiguous().long()
+    dev = preds.device
+    scratch, tp, fp, tn, fn = stat
+    cs = curve.__dict__.get("_hip_onepass_scratch")
+    if cs is None or cs.device != dev or cs.numel() != cs_words:
+        # [P | N1 | N0 copies | n_binned | n_deferred]; the epilogue re-zeroes it
+        cs = torch.zeros(cs_words, dtype=torch.long, device=dev)
+        curve.__dict__["_hip_onepass_scratch"] = cs
+    hist = _pooled_hist(C, T, dev, curve)
+    uni, t0, inv_step = _uniform_params(thr)
+    assert curve.confmat.is_contiguous()
+    rs_ptr = rowstats_buf.data_ptr()
+    rc = lib.ma_mc_onepass_update(
+        _stream(), preds.data_ptr(), dt, target.data_ptr(), preds.shape[0], C,
+        ignore_index if ignore_index is not None else 0,
+        1 if ignore_index is not None else 0,
+        scratch.data_ptr(),
+        confmat.data_ptr() if confmat is not None else 0,
+        tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(),
+        exact[0].data_ptr() if exact is not None else 0,
+        exact[1].data_ptr() if exact is not None else 0,
+        rs_ptr, rs_ptr + 4 * rowstats_buf.shape[1], epoch_buf.data_ptr(),
+        thr.data_ptr(), T, uni, t0, inv_step, hist.data_ptr(), cs.data_ptr(),
+    )
+    _check(rc, "ma_mc_onepass_update")
+    if confmat is not None:
+        _mark_kernel_mutated(confmat)
+    _mark_kernel_mutated(tp)
+    # same lazy protocol as curve_hist_into_confmat: the histogram accumulates,
+    # the suffix/confmat materialization waits for the first state read
+    curve.__dict__["_hip_lazy_meta"] = (C, T, 1)
+    curve.__dict__["_lazy_dirty"] = True
+    return True
