@@ -627,19 +627,10 @@ __global__ void __launch_bounds__(256) k_multiclass_curve_hist(
     int uniform, float t0, float inv_step, int c_chunk,
     int norm_kind /*0 none, 1 softmax (rowstats), 2 sigmoid*/, const unsigned int* __restrict__ E,
     const float* __restrict__ rowmax, const float* __restrict__ rowinv,
-    const unsigned long long* __restrict__ n_deferred /* nullable: skip-done mode */,
     unsigned long long* __restrict__ hist /* (C, T+1, 2) */) {
-    // skip-done mode (deferred pass behind k_mc_onepass, csrc/mc_onepass.hip):
-    // the one-pass kernel already binned every row it could decide on its own
-    // and marked it rowinv < 0; when it deferred nothing, every block leaves
-    // here. The value is final (written by the previous kernel on the stream),
-    // so the exit is uniform across the grid.
-    if (n_deferred && *n_deferred == 0ULL) return;
     extern __shared__ float sthr2[];
     for (int b = threadIdx.x; b < T; b += blockDim.x) sthr2[b] = thresholds[b];
     __syncthreads();
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = threadIdx.x / WAVE;
     // XCD-aware chunk mapping: consecutive blockIdx.x round-robin over the 8
     // XCDs (each with its own L2), but adjacent class-chunks read 8B slices
     // of the SAME cache lines — give each XCD a contiguous band of chunks so
@@ -653,67 +644,11 @@ __global__ void __launch_bounds__(256) k_multiclass_curve_hist(
     }
     const ll c_lo = bx * c_chunk;
     const ll c_hi = min(c_lo + (ll)c_chunk, C);
-    const ll row = (ll)blockIdx.y * 256 + wave * WAVE + lane;
-    bool valid = row < B;
-    ll trow = 0;
-    if (mode == 0 && valid) {
-        trow = target[row];
-        if (has_ignore && trow == ignore_index) valid = false;
-    }
-    if (n_deferred && valid && rowinv[row] < 0.0f) valid = false;  // done in the one-pass kernel
     const int norm = (norm_kind && E && E[0] == E[1] + 1u) ? norm_kind : 0;
-    const float rmax = (norm == 1 && valid) ? rowmax[row] : 0.0f;
-    const float rinv = (norm == 1 && valid) ? rowinv[row] : 0.0f;
-    const T_* prow = probs + (valid ? row * C : 0);
-    const ll* tgt_row = target + (valid ? row * C : 0);
-    // one vector load covers the whole class chunk (4 scalar 2B/4B loads were
-    // the latency bottleneck at small chunks)
-    float pv[4];
-    const bool vec4 = (c_hi - c_lo) == 4 && ((c_lo & 3) == 0) && ((C & 3) == 0);
-    if (valid && vec4) {
-        if (IS_BF16) {
-            ushort4 u = reinterpret_cast<const ushort4*>(prow)[c_lo >> 2];
-            pv[0] = bf16_to_f32(u.x); pv[1] = bf16_to_f32(u.y);
-            pv[2] = bf16_to_f32(u.z); pv[3] = bf16_to_f32(u.w);
-        } else {
-            float4 u = reinterpret_cast<const float4*>(prow)[c_lo >> 2];
-            pv[0] = u.x; pv[1] = u.y; pv[2] = u.z; pv[3] = u.w;
-        }
-    }
-    for (ll c = c_lo; c < c_hi; c++) {
-        int key = -1;
-        if (valid) {
-            int label;
-            if (mode == 0) {
-                label = (trow == c) ? 1 : 0;
-            } else {
-                ll t = tgt_row[c];
-                label = (t == 1) ? 1 : 0;
-                if (has_ignore && t == ignore_index) label = -1;
-            }
-            if (label >= 0) {
-                float p = vec4 ? pv[c - c_lo]
-                               : (IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(prow)[c])
-                                          : (float)prow[c]);
-                if (norm == 1) p = expf(p - rmax) * rinv;
-                else if (norm == 2) p = 1.0f / (1.0f + expf(-p));
-                int j = uniform ? bucket_of_uniform(p, sthr2, T, t0, inv_step)
-                                : bucket_of(p, sthr2, T);
-                key = j * 2 + label;
-            }
-        }
-        // wave-aggregate identical keys -> one atomic per distinct key
-        unsigned long long active = __ballot(key >= 0);
-        while (active) {
-            int leader = __ffsll((unsigned long long)active) - 1;
-            int lkey = __shfl(key, leader);
-            unsigned long long same = __ballot(key == lkey) & active;
-            if (lane == leader)
-                atomicAdd(&hist[(unsigned long long)c * (T + 1) * 2 + lkey],
-                          (unsigned long long)__popcll(same));
-            active &= ~same;
-        }
-    }
+    // the tile body is shared with the one-pass tail kernel (curve_common.h)
+    curve_hist_tile<T_, IS_BF16>(probs, target, B, C, sthr2, T, ignore_index, has_ignore, mode,
+                                 uniform, t0, inv_step, c_lo, c_hi, (ll)blockIdx.y * 256, norm,
+                                 rowmax, rowinv, /*skip_done=*/false, hist);
 }
 
 // LDS-privatized variant: each block owns a (class-chunk x T+1 x 2) uint32
@@ -1539,8 +1474,7 @@ static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uint
                               ll C, uintptr_t thresholds, int T, ll ignore_index, int has_ignore,
                               int mode, int uniform, float t0, float inv_step, int norm_kind,
                               uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv, int variant,
-                              int c_chunk_override, int stats_ready, uintptr_t n_deferred,
-                              uintptr_t hist) {
+                              int c_chunk_override, int stats_ready, uintptr_t hist) {
     hipStream_t s = (hipStream_t)stream;
     size_t shmem = (size_t)T * sizeof(float);
     if (shmem > 160 * 1024) return -100;
@@ -1614,13 +1548,13 @@ static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uint
             (const float*)probs, (const ll*)target, B, C, (const float*)thresholds, T, ignore_index,
             has_ignore, mode, uniform, t0, inv_step, c_chunk, norm_kind,
             (const unsigned int*)flag, (const float*)rowmax, (const float*)rowinv,
-            (const unsigned long long*)n_deferred, (unsigned long long*)hist);
+            (unsigned long long*)hist);
     else
         k_multiclass_curve_hist<unsigned short, true><<<grid, 256, shmem, s>>>(
             (const unsigned short*)probs, (const ll*)target, B, C, (const float*)thresholds, T,
             ignore_index, has_ignore, mode, uniform, t0, inv_step, c_chunk, norm_kind,
             (const unsigned int*)flag, (const float*)rowmax, (const float*)rowinv,
-            (const unsigned long long*)n_deferred, (unsigned long long*)hist);
+            (unsigned long long*)hist);
     return (int)hipGetLastError();
 }
 
@@ -1631,23 +1565,7 @@ int ma_multiclass_curve_hist(uintptr_t stream, uintptr_t probs, int dtype, uintp
                              int c_chunk_override, int stats_ready, uintptr_t hist) {
     return mc_curve_hist_impl(stream, probs, dtype, target, B, C, thresholds, T, ignore_index,
                               has_ignore, mode, uniform, t0, inv_step, norm_kind, flag, rowmax,
-                              rowinv, variant, c_chunk_override, stats_ready, 0, hist);
-}
-
-// Deferred pass behind the one-pass update (csrc/mc_onepass.hip): the
-// ballot-merge kernel in skip-done mode. Exits at once when the one-pass
-// kernel deferred no row; otherwise bins exactly the rows it left (rowinv > 0),
-// softmaxed iff the epoch flag is set.
-int ma_mc_curve_hist_deferred(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target,
-                              ll B, ll C, uintptr_t thresholds, int T, ll ignore_index,
-                              int has_ignore, int uniform, float t0, float inv_step,
-                              uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv,
-                              uintptr_t n_deferred, uintptr_t hist) {
-    if (!n_deferred) return -102;
-    return mc_curve_hist_impl(stream, probs, dtype, target, B, C, thresholds, T, ignore_index,
-                              has_ignore, /*mode=*/0, uniform, t0, inv_step, /*norm_kind=*/1, flag,
-                              rowmax, rowinv, /*variant=*/0, /*c_chunk_override=*/0,
-                              /*stats_ready=*/1, n_deferred, hist);
+                              rowinv, variant, c_chunk_override, stats_ready, hist);
 }
 
 int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int transposed,

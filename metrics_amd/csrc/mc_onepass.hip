@@ -14,9 +14,19 @@
 //           [0,1], the batch-global answer is already known to be "softmax",
 //           and the row is binned from registers right away. A row with every
 //           element in [0,1] cannot know the answer; it is DEFERRED to the
-//           skip-done mode of k_multiclass_curve_hist (kernels.hip), which
-//           runs behind this kernel and exits at once when n_deferred == 0.
-//           There is no grid-wide barrier anywhere.
+//           tail kernel, which runs behind this one and bins exactly those
+//           rows. There is no grid-wide barrier anywhere.
+//
+// TWO LAUNCHES PER STEP. k_mc_onepass ends with ONE 16-byte record per block
+// (valid, binned, deferred + the block's "outside" bit, correct) instead of
+// atomics on single global words: 1024 blocks finishing together on three
+// words serialise. k_onepass_tail reads the records across the kernel
+// boundary; every one of its blocks sums all of them and so knows the
+// batch-global counts and the softmax decision on its own — no epoch flag, no
+// ticket, no wait. Its first ceil(C/256) blocks each apply a class slice of
+// the epilogue, block 0 also the scalars and the epoch bump, and when rows
+// were deferred all blocks grid-stride over the (class-chunk, 256-row) tiles
+// of the deferred pass (curve_hist_tile, shared with kernels.hip).
 //
 // COMPLEMENT IDENTITY: after softmax almost every element of a row falls into
 // one bucket b0 = bucket_of(+0.0f). Those elements issue no atomic at all.
@@ -42,24 +52,32 @@
 typedef long long ll;
 typedef unsigned long long ull;
 
-// curve scratch layout (u64): [P: C][N1: C][N0: NCOPY x C][n_binned][n_deferred]
+// curve scratch layout (u64): [P: C][N1: C][N0: NCOPY x C][records: 2 x GRID_MAX]
 // N0[c] takes ~150 increments per class and step at the bench shape; on one
 // address they serialise (measured: 10 us of the kernel). NCOPY copies, picked
 // by block index (consecutive blocks land on different XCDs), spread them; the
 // epilogue sums the copies.
+// records: one uint4 per k_mc_onepass block, {valid, binned, deferred | outside
+// << 31, correct}. Never zeroed: every launched block overwrites its own record
+// every step and the tail kernel reads exactly `grid` of them. The region
+// starts 80*C bytes into the 16-byte aligned scratch, so it is 16-byte aligned.
 #define ONEPASS_NCOPY 8
-#define ONEPASS_CS_WORDS(C) ((2 + ONEPASS_NCOPY) * (C) + 2)
+#define ONEPASS_GRID_MAX 1024  // records the scratch holds = cap of MA_ONEPASS_GRID
+#define ONEPASS_REC_OFF(C) ((2 + ONEPASS_NCOPY) * (C))
+#define ONEPASS_CS_WORDS(C) (ONEPASS_REC_OFF(C) + 2 * ONEPASS_GRID_MAX)
+#define ONEPASS_TAIL_GRID_DEFAULT 4096  // blocks of k_onepass_tail, see ma_mc_onepass_update
+
 template <bool IS_BF16, int NV>
 __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_onepass(
     const uint4* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
     int has_ignore, ull* __restrict__ tp, ull* __restrict__ fp, ull* __restrict__ fn,
-    ull* __restrict__ confmat, ull* __restrict__ valid_count, float* __restrict__ rowmax,
-    float* __restrict__ rowinv, unsigned int* __restrict__ E,
+    ull* __restrict__ confmat, float* __restrict__ rowmax, float* __restrict__ rowinv,
     const float* __restrict__ thresholds, int T, int uniform, float t0, float inv_step,
-    ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cs /* ONEPASS_CS_WORDS(C) */) {
+    ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cs /* [P|N1|N0 copies] */,
+    uint4* __restrict__ records /* gridDim.x */) {
     constexpr int EPV = IS_BF16 ? 8 : 4;  // elements per 16-byte vector
     extern __shared__ float sthr[];
-    __shared__ unsigned int block_valid, blk_outside, blk_binned, blk_deferred;
+    __shared__ unsigned int block_valid, blk_outside, blk_binned, blk_deferred, blk_correct;
 
     const int lane = threadIdx.x & (WAVE - 1);
     // wave-uniform by construction; tell the compiler, so the row index and
@@ -68,12 +86,11 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     const int waves_per_block = blockDim.x / WAVE;
     const ll row_stride = (ll)gridDim.x * waves_per_block;
     const int nvec = (int)(C / EPV);  // C <= 4096 here: 32-bit class indices
-    const unsigned int cur_epoch = E[1] + 1u;
     ull* __restrict__ cP = cs;
     ull* __restrict__ cN1 = cs + C;
     ull* __restrict__ cN0 = cs + (2 + (blockIdx.x & (ONEPASS_NCOPY - 1))) * C;
     unsigned int outside = 0;
-    unsigned int my_valid = 0, my_binned = 0, my_deferred = 0;
+    unsigned int my_valid = 0, my_binned = 0, my_deferred = 0, my_correct = 0;
 
     auto unpack = [](const uint4& u, float* f) {
         if (IS_BF16) {
@@ -101,7 +118,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     ll row = (ll)blockIdx.x * waves_per_block + wave_in_block;
     if (row < B) load_row(row);
     for (int b = threadIdx.x; b < T; b += blockDim.x) sthr[b] = thresholds[b];
-    if (threadIdx.x == 0) { block_valid = 0; blk_outside = 0; blk_binned = 0; blk_deferred = 0; }
+    if (threadIdx.x == 0) { block_valid = 0; blk_outside = 0; blk_binned = 0; blk_deferred = 0; blk_correct = 0; }
     __syncthreads();
     const int b0 = bucket_of(0.0f, sthr, T);
     const float hi0 = b0 < T ? sthr[b0] : INFINITY;  // bucket b0 is [thr[b0-1], thr[b0])
@@ -162,6 +179,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             if (!ignored && t >= 0 && t < C && p >= 0 && p < C) {
                 my_valid++;
                 if (p == t) {
+                    my_correct++;
                     atomicAdd(&tp[t], 1ULL);
                 } else {
                     atomicAdd(&fp[p], 1ULL);
@@ -240,54 +258,96 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         row += row_stride;
         if (row < B) load_row(row);  // r is dead here: same registers
     }
-    // one atomic per block for each scalar counter
+    // the block's counts meet in LDS; nothing here touches a shared global word
     if (my_valid) atomicAdd(&block_valid, my_valid);
     if (my_binned) atomicAdd(&blk_binned, my_binned);
     if (my_deferred) atomicAdd(&blk_deferred, my_deferred);
+    if (my_correct) atomicAdd(&blk_correct, my_correct);
     for (int off = WAVE / 2; off > 0; off >>= 1) outside |= __shfl_down(outside, off);
     if (lane == 0 && outside) atomicOr(&blk_outside, 1u);
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (block_valid) atomicAdd(valid_count, (ull)block_valid);
-        if (blk_binned) atomicAdd(&cs[(2 + ONEPASS_NCOPY) * C], (ull)blk_binned);
-        if (blk_deferred) atomicAdd(&cs[(2 + ONEPASS_NCOPY) * C + 1], (ull)blk_deferred);
-        if (blk_outside && E[0] != cur_epoch) atomicMax(&E[0], cur_epoch);
+        // one 16-byte store; a block holds < 2^31 rows, so bit 31 is free
+        records[blockIdx.x] = make_uint4(block_valid, blk_binned,
+                                         blk_deferred | (blk_outside << 31), blk_correct);
     }
 }
 
-// Epilogue of the one-pass step: k_apply_stat_exact (stat deltas, optional
-// exact-match) plus the complement fill of bucket b0, in ONE single-block
-// launch. Consumes and re-zeroes both scratches in flight (each slot is read
-// and zeroed by the same thread) and closes the device epoch as its last act.
-__global__ void __launch_bounds__(1024) k_onepass_apply(
+// Tail of the one-pass step, the second and last launch. Every block:
+//  (a) sums the `grid` per-block records of k_mc_onepass (<= 16 KB, L2) and so
+//      holds valid / binned / deferred / outside / correct for the batch;
+//  (b) applies the epilogue for class blockIdx.x*256 + threadIdx.x, if there
+//      is one: k_apply_stat_exact's stat deltas plus the complement fill of
+//      bucket b0. Each slot of both scratches is read and zeroed by the same
+//      thread. The b0 fill is an atomicAdd because in (c) other blocks of this
+//      launch add to the same histogram words. Block 0 also applies the
+//      exact-match scalars and closes the device epoch — at once, since no
+//      block of this kernel reads E: the softmax decision is `outside`;
+//  (c) returns if nothing was deferred (every logits input), else grid-strides
+//      over the (class-chunk, 256-row) tiles of the deferred pass.
+// Nothing written by one block is read by another; there is no ticket, spin
+// or grid-wide wait.
+template <typename T_, bool IS_BF16>
+__global__ void __launch_bounds__(256) k_onepass_tail(
+    const uint4* __restrict__ records, int grid /* blocks k_mc_onepass ran with */,
     ull* __restrict__ scratch /* 3*C + 1 */, ll C, ll B, ll* __restrict__ tp, ll* __restrict__ fp,
     ll* __restrict__ tn, ll* __restrict__ fn, ll* __restrict__ correct /* nullable */,
-    ll* __restrict__ total, unsigned int* __restrict__ E, ull* __restrict__ cs /* ONEPASS_CS_WORDS(C) */,
-    const float* __restrict__ thresholds, int T, ull* __restrict__ hist /* (C, T+1, 2) */) {
-    __shared__ ull part[1024];
-    __shared__ ull valid_s, binned_s;
-    extern __shared__ float sthr_a[];  // a global-memory binary search is ~8 dependent misses
-    for (int b = threadIdx.x; b < T; b += blockDim.x) sthr_a[b] = thresholds[b];
-    if (threadIdx.x == 0) { valid_s = scratch[3 * C]; binned_s = cs[(2 + ONEPASS_NCOPY) * C]; }
+    ll* __restrict__ total, unsigned int* __restrict__ E, ull* __restrict__ cs /* [P|N1|N0 copies] */,
+    const float* __restrict__ thresholds, int T, ull* __restrict__ hist /* (C, T+1, 2) */,
+    const T_* __restrict__ probs, const ll* __restrict__ target, ll ignore_index, int has_ignore,
+    int uniform, float t0, float inv_step, int c_chunk, const float* __restrict__ rowmax,
+    const float* __restrict__ rowinv) {
+    extern __shared__ float sthr_t[];  // a global-memory binary search is ~8 dependent misses
+    __shared__ unsigned int wsum[256 / WAVE][5];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = threadIdx.x / WAVE;
+
+    // ---- (a) the batch-global counts ----
+    unsigned int r_valid = 0, r_binned = 0, r_deferred = 0, r_correct = 0, r_outside = 0;
+    for (int i = threadIdx.x; i < grid; i += blockDim.x) {
+        const uint4 r = records[i];
+        r_valid += r.x;
+        r_binned += r.y;
+        r_deferred += r.z & 0x7fffffffu;
+        r_outside |= r.z >> 31;
+        r_correct += r.w;
+    }
+    for (int b = threadIdx.x; b < T; b += blockDim.x) sthr_t[b] = thresholds[b];
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        r_valid += __shfl_down(r_valid, off);
+        r_binned += __shfl_down(r_binned, off);
+        r_deferred += __shfl_down(r_deferred, off);
+        r_correct += __shfl_down(r_correct, off);
+        r_outside |= __shfl_down(r_outside, off);
+    }
+    if (lane == 0) {
+        wsum[wave][0] = r_valid; wsum[wave][1] = r_binned; wsum[wave][2] = r_deferred;
+        wsum[wave][3] = r_correct; wsum[wave][4] = r_outside;
+    }
     __syncthreads();
-    const ll valid = (ll)valid_s;
-    const ll binned = (ll)binned_s;
-    if (threadIdx.x == 0) { scratch[3 * C] = 0; cs[(2 + ONEPASS_NCOPY) * C] = 0; cs[(2 + ONEPASS_NCOPY) * C + 1] = 0; }
-    const int b0 = bucket_of(0.0f, sthr_a, T);
-    ull acc = 0;
-    for (ll i = threadIdx.x; i < C; i += blockDim.x) {
+    ll valid = 0, binned = 0;
+    unsigned int deferred = 0, ncorrect = 0, outside = 0;
+#pragma unroll
+    for (int w = 0; w < 256 / WAVE; w++) {
+        valid += wsum[w][0]; binned += wsum[w][1]; deferred += wsum[w][2];
+        ncorrect += wsum[w][3]; outside |= wsum[w][4];
+    }
+
+    // ---- (b) epilogue for one class ----
+    const ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < C) {
         const ll dtp = (ll)scratch[i];
         const ll dfp = (ll)scratch[C + i];
         const ll dfn = (ll)scratch[2 * C + i];
         scratch[i] = 0;
         scratch[C + i] = 0;
         scratch[2 * C + i] = 0;
-        acc += (ull)dtp;
         tp[i] += dtp;
         fp[i] += dfp;
         fn[i] += dfn;
         tn[i] += valid - dtp - dfp - dfn;
         if (binned) {  // no row binned => the three counters are already zero
+            const int b0 = bucket_of(0.0f, sthr_t, T);
             const ll P = (ll)cs[i];
             const ll N1 = (ll)cs[C + i];
             ll N0 = 0;
@@ -298,34 +358,53 @@ __global__ void __launch_bounds__(1024) k_onepass_apply(
             }
             cs[i] = 0;
             cs[C + i] = 0;
-            ll* h = (ll*)hist + ((ull)i * (T + 1) + b0) * 2;
-            h[1] += P - N1;
-            h[0] += (binned - P) - N0;
+            ull* h = hist + ((ull)i * (T + 1) + b0) * 2;
+            atomicAdd(&h[1], (ull)(P - N1));
+            atomicAdd(&h[0], (ull)((binned - P) - N0));
         }
     }
-    if (correct) {
-        part[threadIdx.x] = acc;
-        __syncthreads();
-        for (int off = 512; off > 0; off >>= 1) {
-            if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            correct[0] += (ll)part[0] + (B - valid);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (correct) {
+            correct[0] += (ll)ncorrect + (B - valid);  // Σ dtp == the records' correct count
             total[0] += B;
         }
+        E[1] += 1u;
     }
-    if (threadIdx.x == 0) E[1] += 1u;
+
+    // ---- (c) the deferred rows ----
+    if (deferred == 0) return;
+    const int norm = outside ? 1 : 0;  // softmax iff any element of the batch lay outside [0,1]
+    // Tile t -> (class chunk, row tile). Blocks go round-robin over the 8 XCDs
+    // (each with its own L2) and adjacent class chunks read slices of the SAME
+    // cache lines, so XCD x = t % 8 (the grid is a multiple of 8) keeps to a
+    // contiguous band of chunks, as k_multiclass_curve_hist does; the
+    // c_chunks % 8 leftover chunks come last.
+    const ll c_chunks = (C + c_chunk - 1) / c_chunk;
+    const ll row_chunks = (B + 255) / 256;
+    const ll band = c_chunks / 8;
+    const ll rem = c_chunks - band * 8;
+    const ll nmain = band * 8 * row_chunks;
+    const ll ntiles = c_chunks * row_chunks;
+    for (ll t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        ll chunk, ry;
+        if (t < nmain) {
+            const ll u = t >> 3;
+            chunk = (t & 7) * band + u % band;
+            ry = u / band;
+        } else {
+            const ll u = t - nmain;
+            chunk = band * 8 + u % rem;
+            ry = u / rem;
+        }
+        const ll c_lo = chunk * c_chunk;
+        const ll c_hi = min(c_lo + (ll)c_chunk, C);
+        curve_hist_tile<T_, IS_BF16>(probs, target, B, C, sthr_t, T, ignore_index, has_ignore,
+                                     /*mode=*/0, uniform, t0, inv_step, c_lo, c_hi, ry * 256, norm,
+                                     rowmax, rowinv, /*skip_done=*/true, hist);
+    }
 }
 
 extern "C" {
-
-// kernels.hip
-int ma_mc_curve_hist_deferred(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target,
-                              ll B, ll C, uintptr_t thresholds, int T, ll ignore_index,
-                              int has_ignore, int uniform, float t0, float inv_step,
-                              uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv,
-                              uintptr_t n_deferred, uintptr_t hist);
 
 // NV (16-byte vectors per lane) the one-pass kernel would use, 0 = unsupported
 // shape (caller keeps the two-kernel path). NV in {1,2,4,8}; NV <= 2 (bf16
@@ -343,22 +422,48 @@ int ma_mc_onepass_nv(int dtype /*0=f32 1=bf16*/, ll C, int T) {
     return nv;
 }
 
-// u64 words of the curve scratch for C classes
+// u64 words of the curve scratch for C classes (records region included)
 int ma_mc_onepass_scratch_words(ll C) { return (int)ONEPASS_CS_WORDS(C); }
 
-#define ONEPASS_LAUNCH(BF, NV_)                                                                   \
-    k_mc_onepass<BF, NV_><<<grid, 256, shmem, s>>>(                                               \
-        (const uint4*)preds, (const ll*)target, B, C, ignore_index, has_ignore, sc, sc + C,       \
-        sc + 2 * C, (ull*)confmat, sc + 3 * C, (float*)rowmax, (float*)rowinv,                    \
-        (unsigned int*)epoch_buf, (const float*)thresholds, T, uniform, t0, inv_step, (ull*)hist, \
-        (ull*)cscratch)
+#define ONEPASS_LAUNCH(BF, NV_)                                                                  \
+    k_mc_onepass<BF, NV_><<<grid, 256, shmem, s>>>(                                              \
+        (const uint4*)preds, (const ll*)target, B, C, ignore_index, has_ignore, sc, sc + C,      \
+        sc + 2 * C, (ull*)confmat, (float*)rowmax, (float*)rowinv, (const float*)thresholds, T,  \
+        uniform, t0, inv_step, (ull*)hist, (ull*)cscratch, records)
 
-// The whole fused-collection step on one stream: one-pass kernel, deferred
-// histogram pass (early exit when nothing was deferred), epilogue.
-// scratch = stat scratch [tp|fp|fn|valid] (3*C+1 u64), cscratch = curve
-// scratch [P|N1|N0 copies|n_binned|n_deferred] (ma_mc_onepass_scratch_words(C)
-// u64); both zero on entry and
-// zero again after the epilogue. correct/total may be 0 (no exact-match leader).
+#define ONEPASS_TAIL_LAUNCH(T_, BF)                                                              \
+    k_onepass_tail<T_, BF><<<tgrid, 256, shmem, s>>>(                                            \
+        records, grid, (ull*)scratch, C, B, (ll*)tp, (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct,    \
+        (ll*)total, (unsigned int*)epoch_buf, (ull*)cscratch, (const float*)thresholds, T,       \
+        (ull*)hist, (const T_*)preds, (const ll*)target, ignore_index, has_ignore, uniform, t0,  \
+        inv_step, c_chunk, (const float*)rowmax, (const float*)rowinv)
+
+// blocks of k_mc_onepass for B rows: one row per wave and pass, 4 waves per
+// block. Measured at B=8192 C=1000 (sweep knob MA_ONEPASS_GRID): 2048 blocks —
+// every row resident at once — run the load, fold and binning phases chip-wide
+// in lock step (53 us/step); with 512-1024 blocks each wave takes several
+// rows, the waves drift apart and the phases overlap (45 us). The knob is
+// clamped to the records the scratch holds.
+static int onepass_grid(ll B) {
+    static int gcap = 0;
+    if (gcap == 0) {
+        const char* e = getenv("MA_ONEPASS_GRID");
+        gcap = e ? atoi(e) : 1024;
+        if (gcap < 64) gcap = 64;
+        if (gcap > ONEPASS_GRID_MAX) gcap = ONEPASS_GRID_MAX;
+    }
+    ll g = (B + 3) / 4;
+    if (g > gcap) g = gcap;
+    return (int)g;
+}
+
+// The whole fused-collection step on one stream in two launches: one-pass
+// kernel, tail kernel (B == 0: the tail alone, which then is the epilogue).
+// scratch = stat scratch [tp|fp|fn|valid] (3*C+1 u64; the valid slot is not
+// used here), cscratch = curve scratch [P|N1|N0 copies|records]
+// (ma_mc_onepass_scratch_words(C) u64); the counters of both are zero on entry
+// and zero again after the tail, the records need no zeroing.
+// correct/total may be 0 (no exact-match leader).
 int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t target, ll B,
                          ll C, ll ignore_index, int has_ignore, uintptr_t scratch,
                          uintptr_t confmat, uintptr_t tp, uintptr_t fp, uintptr_t tn, uintptr_t fn,
@@ -367,27 +472,15 @@ int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
                          float inv_step, uintptr_t hist, uintptr_t cscratch) {
     hipStream_t s = (hipStream_t)stream;
     const int nv = ma_mc_onepass_nv(dtype, C, T);
-    if (nv == 0 || (preds & 15) || !scratch || !cscratch || !hist || !rowmax || !rowinv ||
-        !epoch_buf || !thresholds)
+    if (nv == 0 || (preds & 15) || (cscratch & 15) || !scratch || !cscratch || !hist || !rowmax ||
+        !rowinv || !epoch_buf || !thresholds)
         return -103;
-    if ((B + 255) / 256 > 65535) return -101;  // the deferred pass's grid.y limit
+    if (B < 0 || B >= (1LL << 31)) return -101;  // u32 counts in the records
+    const size_t shmem = (size_t)T * sizeof(float);
+    uint4* records = (uint4*)((ull*)cscratch + ONEPASS_REC_OFF(C));
+    const int grid = B > 0 ? onepass_grid(B) : 0;
     if (B > 0) {
         ull* sc = (ull*)scratch;
-        const size_t shmem = (size_t)T * sizeof(float);
-        // one row per wave and pass, 4 waves per block. Measured at B=8192
-        // C=1000 (sweep knob MA_ONEPASS_GRID): 2048 blocks — every row
-        // resident at once — run the load, fold and binning phases chip-wide
-        // in lock step (53 us/step); with 512-1024 blocks each wave takes
-        // several rows, the waves drift apart and the phases overlap (45 us)
-        static int gcap = 0;
-        if (gcap == 0) {
-            const char* e = getenv("MA_ONEPASS_GRID");
-            gcap = e ? atoi(e) : 1024;
-            if (gcap < 64) gcap = 64;
-        }
-        ll g = (B + 3) / 4;
-        if (g > gcap) g = gcap;
-        const int grid = (int)g;
         if (dtype == 1) {
             if (nv == 1) ONEPASS_LAUNCH(true, 1);
             else if (nv == 2) ONEPASS_LAUNCH(true, 2);
@@ -401,15 +494,34 @@ int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
-        int rc = ma_mc_curve_hist_deferred(stream, preds, dtype, target, B, C, thresholds, T,
-                                           ignore_index, has_ignore, uniform, t0, inv_step,
-                                           epoch_buf, rowmax, rowinv,
-                                           cscratch + (uintptr_t)((2 + ONEPASS_NCOPY) * C + 1) * sizeof(ull), hist);
-        if (rc != 0) return rc;
     }
-    k_onepass_apply<<<1, 1024, (size_t)T * sizeof(float), s>>>((ull*)scratch, C, B, (ll*)tp, (ll*)fp, (ll*)tn, (ll*)fn,
-                                       (ll*)correct, (ll*)total, (unsigned int*)epoch_buf,
-                                       (ull*)cscratch, (const float*)thresholds, T, (ull*)hist);
+    // Tail grid: a function of B and C alone (nothing only the device knows).
+    // The first ceil(C/256) blocks carry the epilogue; the rest exist for the
+    // deferred tiles and, with logit inputs, sum the records and leave. Class
+    // chunks as in the two-kernel path: 4 classes, halved while the tile count
+    // stays small. Sweep knob MA_ONEPASS_TAIL_GRID (profiles/README.md): 2048
+    // blocks fill every CU, but the deferred tiles differ in cost (atomics),
+    // and with a static walk the slowest block sets the time; twice as many
+    // blocks as fit lets the dispatcher balance them (torch.rand inputs 361 us
+    // at 2048, 347 at 4000, the three-launch step 347-348) for 2.5 us of the
+    // logits loop.
+    static int tcap = 0;
+    if (tcap == 0) {
+        const char* e = getenv("MA_ONEPASS_TAIL_GRID");
+        tcap = e ? atoi(e) : ONEPASS_TAIL_GRID_DEFAULT;
+        if (tcap < 8) tcap = 8;
+        if (tcap > 65536) tcap = 65536;
+    }
+    const ll row_chunks = (B + 255) / 256;
+    int c_chunk = 4;
+    while (c_chunk > 1 && ((C + c_chunk - 1) / c_chunk) * row_chunks < 4096) c_chunk /= 2;
+    const ll ntiles = ((C + c_chunk - 1) / c_chunk) * row_chunks;
+    ll tg = ntiles < tcap ? ntiles : tcap;
+    const ll eblocks = (C + 255) / 256;
+    if (tg < eblocks) tg = eblocks;
+    const int tgrid = (int)((tg + 7) / 8 * 8);  // multiple of 8: block % 8 is the XCD
+    if (dtype == 1) ONEPASS_TAIL_LAUNCH(unsigned short, true);
+    else ONEPASS_TAIL_LAUNCH(float, false);
     return (int)hipGetLastError();
 }
 

@@ -1440,8 +1440,8 @@ def mc_onepass_update(
 ) -> bool:
     """The whole fused-collection step (stat scores, confusion matrix, exact
     match, threshold-curve histogram) in ONE native call that reads the logits
-    once: one-pass kernel + deferred histogram pass + epilogue, all enqueued on
-    the current stream. No allocation in steady state and no host sync, so it
+    once: one-pass kernel + tail kernel (epilogue and deferred rows), two
+    launches on the current stream. No allocation in steady state and no host sync, so it
     is hipGraph-capturable.
 
     Returns False without launching anything when the shape is not covered
@@ -1472,7 +1472,8 @@ def mc_onepass_update(
     scratch, tp, fp, tn, fn = stat
     cs = curve.__dict__.get("_hip_onepass_scratch")
     if cs is None or cs.device != dev or cs.numel() != cs_words:
-        # [P | N1 | N0 copies | n_binned | n_deferred]; the epilogue re-zeroes it
+        # [P | N1 | N0 copies | per-block records]; the tail kernel re-zeroes
+        # the counters, the records are overwritten every step
         cs = torch.zeros(cs_words, dtype=torch.long, device=dev)
         curve.__dict__["_hip_onepass_scratch"] = cs
     hist = _pooled_hist(C, T, dev, curve)
