@@ -35,6 +35,13 @@ from metrics_amd.functional.classification.precision_recall_curve import (
 )
 
 
+def _curve_kernels_cover(thresholds: Tensor) -> bool:
+    """Threshold counts past the kernels' LDS budget take the torch path."""
+    from metrics_amd.ops import _hip
+
+    return _hip.curve_kernels_cover(thresholds.numel())
+
+
 class BinaryPrecisionRecallCurve(Metric):
     """PR curve for binary tasks (stateful)."""
 
@@ -73,7 +80,12 @@ class BinaryPrecisionRecallCurve(Metric):
         """Accumulate either (preds, target) lists or the (T,2,2) confmat."""
         if self.validate_args:
             _binary_precision_recall_curve_tensor_validation(preds, target, self.ignore_index)
-        gpu_fast = preds.is_cuda and self.thresholds is not None and preds.dtype in (torch.float32, torch.bfloat16)
+        gpu_fast = (
+            preds.is_cuda
+            and self.thresholds is not None
+            and preds.dtype in (torch.float32, torch.bfloat16)
+            and _curve_kernels_cover(self.thresholds)
+        )
         remove_ignored = not gpu_fast
         preds_f, target_f, _ = _binary_precision_recall_curve_format(
             preds, target, self.thresholds, self.ignore_index, remove_ignored=remove_ignored,
@@ -167,6 +179,7 @@ class MulticlassPrecisionRecallCurve(Metric):
             and self.thresholds is not None
             and self.average != "micro"
             and preds.dtype in (torch.float32, torch.bfloat16)
+            and _curve_kernels_cover(self.thresholds)
         )
         remove_ignored = not gpu_fast
         preds_f, target_f, _ = _multiclass_precision_recall_curve_format(
@@ -249,7 +262,12 @@ class MultilabelPrecisionRecallCurve(Metric):
         """Accumulate either (preds, target) lists or the (T,L,2,2) confmat."""
         if self.validate_args:
             _multilabel_precision_recall_curve_tensor_validation(preds, target, self.num_labels, self.ignore_index)
-        gpu_fast = preds.is_cuda and self.thresholds is not None and preds.dtype in (torch.float32, torch.bfloat16)
+        gpu_fast = (
+            preds.is_cuda
+            and self.thresholds is not None
+            and preds.dtype in (torch.float32, torch.bfloat16)
+            and _curve_kernels_cover(self.thresholds)
+        )
         remove_ignored = not preds.is_cuda
         preds_f, target_f, _ = _multilabel_precision_recall_curve_format(
             preds, target, self.num_labels, self.thresholds, self.ignore_index, remove_ignored=remove_ignored,

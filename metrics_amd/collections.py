@@ -77,8 +77,11 @@ class _FusedMulticlassUpdatePlan:
             elif kind == "mc_curve" and curve is None:
                 import os
 
+                from metrics_amd.ops import _hip
+
                 if (
                     leader.thresholds is not None
+                    and _hip.curve_kernels_cover(leader.thresholds.numel())
                     and getattr(leader, "average", None) != "micro"
                     and os.environ.get("METRICS_AMD_FUSE_CURVE", "1") != "0"
                 ):

@@ -27,8 +27,13 @@ __device__ __forceinline__ int bucket_of(float p, const float* __restrict__ thr,
 // bit-identical to the binary search at ~2 LDS reads instead of log2(T).
 __device__ __forceinline__ int bucket_of_uniform(float p, const float* __restrict__ thr, int T,
                                                  float t0, float inv_step) {
-    int j = (int)floorf((p - t0) * inv_step) + 1;
-    j = j < 0 ? 0 : (j > T ? T : j);
+    // clamp in float BEFORE the conversion: (int) of a NaN or of a value past
+    // INT_MAX is undefined. fmaxf drops a NaN operand, so a NaN score starts at
+    // j = 0 and stays there (both fixups compare false) — bucket 0, negative
+    // at every threshold, exactly as bucket_of and `score >= thr` have it.
+    float g = floorf((p - t0) * inv_step);
+    g = fminf(fmaxf(g, -1.0f), (float)(T - 1));
+    int j = (int)g + 1;
     while (j < T && thr[j] <= p) j++;
     while (j > 0 && thr[j - 1] > p) j--;
     return j;

@@ -70,13 +70,14 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
         float best = -INFINITY;
         ll best_idx = 0x7fffffffffffffffLL;
         float sm_m = -3.4e38f, sm_s = 0.0f;  // online softmax (max, sumexp)
+        unsigned int row_out = 0;
         auto stats_fold = [&](const float* f, int k) {
             if (!want_stats) return;
             float m8 = f[0];
             for (int i = 1; i < k; i++) m8 = fmaxf(m8, f[i]);
             float s8 = 0.0f;
             for (int i = 0; i < k; i++) {
-                outside |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
+                row_out |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
                 s8 += __expf(f[i] - m8);
             }
             if (m8 > sm_m) { sm_s = sm_s * __expf(sm_m - m8) + s8; sm_m = m8; }
@@ -150,10 +151,14 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
             ll oi = __shfl_down(best_idx, off);
             if (ov > best || (ov == best && oi < best_idx)) { best = ov; best_idx = oi; }
         }
+        // the row's range bit lands in lane 0, which holds the target: an
+        // ignored row takes no part in the softmax decision (reference order)
+        const bool row_any_out = want_stats && __ballot(row_out != 0u) != 0ULL;
         if (lane == 0) {
             ll t = target[row];
             ll p = best_idx;
             if (argmax_out) argmax_out[row] = p;
+            if (row_any_out && !(has_ignore && t == ignore_index)) outside = 1u;
             // bounds guard: bad labels with validate_args=False must not corrupt memory
             if (!(has_ignore && t == ignore_index) && t >= 0 && t < C && p >= 0 && p < C) {
                 my_valid++;
@@ -217,10 +222,11 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits_tiny(
         float best = -INFINITY;
         ll best_idx = 0;
         float sm_m = -3.4e38f, sm_s = 0.0f;
+        unsigned int row_out = 0;
         auto fold = [&](float f, ll c) {
             if (f > best) { best = f; best_idx = c; }
             if (want_stats) {
-                outside |= (f < 0.0f || f > 1.0f) ? 1u : 0u;
+                row_out |= (f < 0.0f || f > 1.0f) ? 1u : 0u;
                 if (f > sm_m) { sm_s = sm_s * __expf(sm_m - f) + 1.0f; sm_m = f; }
                 else { sm_s += __expf(f - sm_m); }
             }
@@ -249,6 +255,8 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits_tiny(
         ll t = target[row];
         ll p = best_idx;
         if (argmax_out) argmax_out[row] = p;
+        // an ignored row takes no part in the softmax decision (reference order)
+        outside |= (has_ignore && t == ignore_index) ? 0u : row_out;
         if (!(has_ignore && t == ignore_index) && t >= 0 && t < C && p >= 0 && p < C) {
             my_valid++;
             if (p == t) {
@@ -395,10 +403,12 @@ __global__ void __launch_bounds__(256) k_binary_stat(
     unsigned int outside = 0;
     for (; i < N; i += stride) {
         ll t = target[i];
-        if (has_ignore && t == ignore_index) continue;
         float p = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(preds)[i])
                           : (float)preds[i];
+        // the range test sees ignored elements too (reference: sigmoid iff ANY
+        // element lies outside [0,1], decided before the ignore mask applies)
         outside |= (p < 0.0f || p > 1.0f) ? 1u : 0u;
+        if (has_ignore && t == ignore_index) continue;
         int pr_raw = p > threshold;
         int pr_sig = p > logit_thr;
         int tt = (int)t;
@@ -444,10 +454,12 @@ __global__ void __launch_bounds__(256) k_multilabel_stat(
     for (; i < N * L; i += stride) {
         ll l = i % L;
         ll t = target[i];
-        if (has_ignore && t == ignore_index) continue;
         float p = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(preds)[i])
                           : (float)preds[i];
+        // the range test sees ignored elements too (reference: sigmoid iff ANY
+        // element lies outside [0,1], decided before the ignore mask applies)
         outside |= (p < 0.0f || p > 1.0f) ? 1u : 0u;
+        if (has_ignore && t == ignore_index) continue;
         int pr_raw = p > threshold;
         int pr_sig = p > logit_thr;
         int tt = (int)t;
@@ -482,14 +494,19 @@ __global__ void __launch_bounds__(256) k_multilabel_stat(
 // DEVICE-epoch protocol (hipGraph-capturable, no host state): E[1] counts
 // completed curve updates (bumped by k_curve_suffix), E[0] records the epoch
 // whose inputs were out-of-range. "Normalize this update" <=> E[0] == E[1]+1.
+// has_ignore (binary curve only): samples whose target is ignore_index are
+// removed BEFORE the range test, as in the reference; the multilabel curve
+// tests every element and passes has_ignore = 0.
 template <typename T_, bool IS_BF16>
 __global__ void __launch_bounds__(256) k_range_flag(
-    const T_* __restrict__ x, ll N, unsigned int* __restrict__ E) {
+    const T_* __restrict__ x, ll N, const ll* __restrict__ target, ll ignore_index,
+    int has_ignore, unsigned int* __restrict__ E) {
     const unsigned int cur = E[1] + 1u;  // stable: only k_curve_suffix writes E[1]
     ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
     ll stride = (ll)gridDim.x * blockDim.x;
     unsigned int outside = 0;
     for (; i < N; i += stride) {
+        if (has_ignore && target[i] == ignore_index) continue;
         float p = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(x)[i])
                           : (float)x[i];
         outside |= (p < 0.0f || p > 1.0f) ? 1u : 0u;
@@ -509,8 +526,9 @@ __global__ void __launch_bounds__(256) k_range_flag(
 // plus the outside-[0,1] flag. Wave per row, lanes stride classes (coalesced).
 template <typename T_, bool IS_BF16>
 __global__ void __launch_bounds__(256) k_mc_rowstats(
-    const T_* __restrict__ probs, ll B, ll C, unsigned int* __restrict__ E,
-    float* __restrict__ rowmax, float* __restrict__ rowinv) {
+    const T_* __restrict__ probs, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
+    int has_ignore, unsigned int* __restrict__ E, float* __restrict__ rowmax,
+    float* __restrict__ rowinv) {
     const unsigned int cur = E[1] + 1u;
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x / WAVE;
@@ -523,12 +541,16 @@ __global__ void __launch_bounds__(256) k_mc_rowstats(
         // online softmax merged 8 elements at a time; 16B vector loads per
         // lane (scalar 2B loads were 3.5x slower: latency-bound)
         float m = -3.4e38f, s = 0.0f;
+        // an ignored row takes no part in the range test (the reference drops
+        // ignored samples before it); one wave-uniform load, only with has_ignore
+        unsigned int row_out = 0;
+        const bool row_ignored = has_ignore && target[row] == ignore_index;
         auto fold8 = [&](const float* f, int k) {
             float m8 = f[0];
             for (int i = 1; i < k; i++) m8 = fmaxf(m8, f[i]);
             float s8 = 0.0f;
             for (int i = 0; i < k; i++) {
-                outside |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
+                row_out |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
                 s8 += __expf(f[i] - m8);
             }
             if (m8 > m) { s = s * __expf(m - m8) + s8; m = m8; }
@@ -567,6 +589,7 @@ __global__ void __launch_bounds__(256) k_mc_rowstats(
             else { s += os * __expf(om - m); }
         }
         if (lane == 0) { rowmax[row] = m; rowinv[row] = 1.0f / s; }
+        outside |= row_ignored ? 0u : row_out;
     }
     __shared__ unsigned int blk_outside2;
     if (threadIdx.x == 0) blk_outside2 = 0;
@@ -1452,10 +1475,12 @@ int ma_binary_curve_hist(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
     if (norm_sigmoid && flag) {
         if (dtype == 0)
             k_range_flag<float, false><<<grid_for(N, 256), 256, 0, s>>>(
-                (const float*)preds, N, (unsigned int*)flag);
+                (const float*)preds, N, (const ll*)target, ignore_index, has_ignore,
+                (unsigned int*)flag);
         else
             k_range_flag<unsigned short, true><<<grid_for(N, 256), 256, 0, s>>>(
-                (const unsigned short*)preds, N, (unsigned int*)flag);
+                (const unsigned short*)preds, N, (const ll*)target, ignore_index, has_ignore,
+                (unsigned int*)flag);
     }
     if (dtype == 0)
         k_binary_curve_hist<float, false><<<grid_for(N, 256), 256, shmem, s>>>(
@@ -1491,21 +1516,25 @@ static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uint
         int grid = grid_for(B, rows_div);
         if (dtype == 0)
             k_mc_rowstats<float, false><<<grid, 256, 0, s>>>(
-                (const float*)probs, B, C, (unsigned int*)flag, (float*)rowmax, (float*)rowinv);
+                (const float*)probs, (const ll*)target, B, C, ignore_index,
+                has_ignore && mode == 0, (unsigned int*)flag, (float*)rowmax, (float*)rowinv);
         else
             k_mc_rowstats<unsigned short, true><<<grid, 256, 0, s>>>(
-                (const unsigned short*)probs, B, C, (unsigned int*)flag, (float*)rowmax,
-                (float*)rowinv);
+                (const unsigned short*)probs, (const ll*)target, B, C, ignore_index,
+                has_ignore && mode == 0, (unsigned int*)flag, (float*)rowmax, (float*)rowinv);
     } else if (norm_kind == 2 && flag) {
         if (dtype == 0)
             k_range_flag<float, false><<<grid_for(B * C, 256), 256, 0, s>>>(
-                (const float*)probs, B * C, (unsigned int*)flag);
+                (const float*)probs, B * C, (const ll*)nullptr, 0, 0, (unsigned int*)flag);
         else
             k_range_flag<unsigned short, true><<<grid_for(B * C, 256), 256, 0, s>>>(
-                (const unsigned short*)probs, B * C, (unsigned int*)flag);
+                (const unsigned short*)probs, B * C, (const ll*)nullptr, 0, 0,
+                (unsigned int*)flag);
     }
     // LDS-privatized variant when the per-block histogram fits comfortably
-    const int lds_c_chunk = c_chunk_override > 0 ? c_chunk_override : 32;
+    // the kernel maps 32 threads to the classes of a chunk: a wider chunk would
+    // leave classes 32.. of every chunk unread, so an override above 32 is clamped
+    const int lds_c_chunk = c_chunk_override > 0 ? (c_chunk_override < 32 ? c_chunk_override : 32) : 32;
     const size_t lds_bytes = (size_t)lds_c_chunk * (T + 1) * 2 * sizeof(unsigned int)
                              + (size_t)T * sizeof(float);
     // measured (tools/curve_sweep.py, B=8192 C=1000 T=200): ballot-merge with a
@@ -1593,8 +1622,9 @@ int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int trans
             return (int)hipGetLastError();
         }
     }
+    // k_curve_suffix also holds two static __shared__ u64 totals
     size_t shmem = (size_t)(T + 1) * 2 * sizeof(unsigned long long);
-    if (shmem > 160 * 1024) return -100;
+    if (shmem + 2 * sizeof(unsigned long long) > 160 * 1024) return -100;
     k_curve_suffix<<<(int)outer, 256, shmem, s>>>((unsigned long long*)hist, T, outer, transposed,
                                                   zero_hist, (unsigned int*)epoch_buf,
                                                   (ll*)confmat);

@@ -155,6 +155,10 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
                 }
             }
         }
+        // an ignored row takes no part in the softmax decision (the reference
+        // drops ignored samples before the range test); t is already loaded
+        const bool ignored = has_ignore && t == ignore_index;
+        if (ignored) row_out = 0u;
         outside |= row_out;
         for (int off = WAVE / 2; off > 0; off >>= 1) {
             float om = __shfl_down(sm_m, off);
@@ -170,7 +174,6 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         // lane 0 holds the row's (max, sumexp); every lane needs them for phase B
         const float rmax = __shfl(sm_m, 0);
         const float rinv = __shfl(1.0f / sm_s, 0);
-        const bool ignored = has_ignore && t == ignore_index;
         const bool certain = __ballot(row_out != 0u) != 0ULL;  // this row alone proves "softmax"
         const bool bin_now = certain && !ignored;
         if (lane == 0) {

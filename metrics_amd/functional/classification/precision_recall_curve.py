@@ -144,7 +144,9 @@ def _binary_precision_recall_curve_format(
         target = target[idx]
 
     if normalize:
-        preds = normalize_logits_if_needed(preds, "sigmoid")
+        # ignored samples left in for the kernel still take no part in the range test
+        keep = target != ignore_index if (ignore_index is not None and not remove_ignored) else None
+        preds = normalize_logits_if_needed(preds, "sigmoid", keep)
     thresholds = _adjust_threshold_arg(thresholds, preds.device)
     return preds, target, thresholds
 
@@ -275,7 +277,9 @@ def _multiclass_precision_recall_curve_format(
         target = target[idx]
 
     if normalize:
-        preds = normalize_logits_if_needed(preds, "softmax")
+        # ignored samples left in for the kernel still take no part in the range test
+        keep = target != ignore_index if (ignore_index is not None and not remove_ignored) else None
+        preds = normalize_logits_if_needed(preds, "softmax", keep)
 
     if average == "micro":
         preds = preds.flatten()

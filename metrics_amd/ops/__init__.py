@@ -119,8 +119,11 @@ def binary_curve_confmat(
     preds: Tensor, target: Tensor, thresholds: Tensor, ignore_index: Optional[int] = None
 ) -> Tensor:
     """(T,2,2) binary threshold confmat. GPU: bucketized histogram kernel."""
-    if preds.is_cuda:
+    if preds.is_cuda and _hip.curve_kernels_cover(len(thresholds)):
         return _hip.binary_curve_confmat(preds, target, thresholds, ignore_index)
+    if ignore_index is not None:  # only GPU callers leave the mask to the kernel
+        keep = target != ignore_index
+        preds, target = preds[keep], target[keep]
     len_t = len(thresholds)
     preds_t = (preds.unsqueeze(-1) >= thresholds.unsqueeze(0)).long()  # (N, T)
     unique_mapping = preds_t + 2 * target.long().unsqueeze(-1) + 4 * torch.arange(len_t, device=target.device)
@@ -132,8 +135,11 @@ def multiclass_curve_confmat(
     probs: Tensor, target: Tensor, thresholds: Tensor, ignore_index: Optional[int] = None
 ) -> Tensor:
     """(T,C,2,2) one-vs-rest threshold confmats; ``probs`` (B,C) normalized."""
-    if probs.is_cuda:
+    if probs.is_cuda and _hip.curve_kernels_cover(len(thresholds)):
         return _hip.multiclass_curve_confmat(probs, target, thresholds, ignore_index, mode=0)
+    if ignore_index is not None:  # only GPU callers leave the mask to the kernel
+        keep = target != ignore_index
+        probs, target = probs[keep], target[keep]
     len_t = len(thresholds)
     num_classes = probs.shape[1]
     target_t = torch.nn.functional.one_hot(target, num_classes=num_classes)
@@ -178,14 +184,17 @@ def multilabel_curve_confmat(
 ) -> Tensor:
     """(T,L,2,2) per-label threshold confmats; ``probs`` (B,L) normalized.
 
-    On GPU, elements with target == ignore_index are skipped in-kernel; the
-    CPU path expects callers to pre-mask (reference semantics use -1 sentinel
-    handled here by clamping counts of negative targets away).
+    On GPU, elements with target == ignore_index are skipped in-kernel. The
+    torch path (CPU, or more thresholds than the kernels hold) maps them to a
+    negative bin that is dropped, like the sentinel callers may have set already.
     """
-    if probs.is_cuda:
+    if probs.is_cuda and _hip.curve_kernels_cover(len(thresholds)):
         return _hip.multiclass_curve_confmat(probs, target, thresholds, ignore_index, mode=1)
     len_t = len(thresholds)
     num_labels = probs.shape[1]
+    if ignore_index is not None:  # only GPU callers leave the mask to the kernel
+        target = target.clone()
+        target[target == ignore_index] = -4 * num_labels * len_t  # negative mapping, dropped below
     preds_t = (probs.unsqueeze(-1) >= thresholds[None, None, :]).long()
     unique_mapping = preds_t + 2 * target.long().unsqueeze(-1)
     unique_mapping += 4 * torch.arange(num_labels, device=probs.device)[None, :, None]

@@ -305,6 +305,19 @@ _ROWSTATS_POOL: dict = {}
 _CURVE_VARIANT = int(os.environ.get("METRICS_AMD_CURVE_VARIANT", "-1"))
 _CURVE_CCHUNK = int(os.environ.get("METRICS_AMD_CURVE_CCHUNK", "0"))
 
+# Largest threshold count the curve kernels serve. The binding limit is
+# k_curve_suffix (the only suffix kernel left once the tiled one no longer
+# fits): (T+1)*2 u64 of dynamic LDS plus its two static u64 totals against the
+# 160 KiB of a gfx950 workgroup, i.e. 16*(T+1) + 16 <= 163840. The histogram
+# kernels reach further (binary: 12*T + 8 bytes, T <= 13652; multiclass: 4*T
+# bytes), so the suffix bound decides. Callers route larger T to the torch path.
+CURVE_MAX_T = (160 * 1024 - 16) // 16 - 1  # 10238
+
+
+def curve_kernels_cover(num_thresholds: int) -> bool:
+    """True if the threshold-curve kernels can hold ``num_thresholds`` in LDS."""
+    return int(num_thresholds) <= CURVE_MAX_T
+
 
 def _epoch_buf(device, owner=None) -> Tensor:
     """Device-epoch buffer E (2 x uint32). Owned per-METRIC when ``owner`` is

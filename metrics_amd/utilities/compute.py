@@ -91,8 +91,13 @@ def auc(x: Tensor, y: Tensor, reorder: bool = False) -> Tensor:
     return _auc_compute(x, y, reorder=reorder)
 
 
-def normalize_logits_if_needed(tensor: Tensor, normalization: str) -> Tensor:
+def normalize_logits_if_needed(tensor: Tensor, normalization: str, keep: Optional[Tensor] = None) -> Tensor:
     """Apply sigmoid/softmax iff values fall outside [0, 1].
+
+    ``keep`` (bool, one entry per sample along dim 0) restricts the range test
+    to the kept samples: the binary and multiclass curve formats drop ignored
+    samples BEFORE the test, and GPU callers that leave the mask to the kernel
+    pass it here so the decision is the same.
 
     Single-pass check; we control the device and accept the device sync the
     ``.any()`` implies only on CPU — on GPU the branchless torch.where form is
@@ -100,6 +105,14 @@ def normalize_logits_if_needed(tensor: Tensor, normalization: str) -> Tensor:
     normalize in-kernel).
     """
     assert normalization in ("sigmoid", "softmax")
+    if keep is not None:
+        outside = (tensor < 0) | (tensor > 1)
+        condition = (outside & keep.reshape(-1, *([1] * (tensor.ndim - 1)))).any()
+        return torch.where(
+            condition,
+            torch.sigmoid(tensor) if normalization == "sigmoid" else torch.softmax(tensor, dim=-1),
+            tensor,
+        )
     if tensor.device.type == "cpu":
         if not torch.all((tensor >= 0) * (tensor <= 1)):
             tensor = tensor.sigmoid() if normalization == "sigmoid" else tensor.softmax(dim=-1)
