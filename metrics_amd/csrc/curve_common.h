@@ -6,10 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
-__device__ __forceinline__ float bf16_to_f32(unsigned short u) {
-    unsigned int v = ((unsigned int)u) << 16;
-    return __uint_as_float(v);
-}
+#include "row_fold.h"
 
 // bucket j = #thresholds <= p  (searchsorted right) in [0, T]
 __device__ __forceinline__ int bucket_of(float p, const float* __restrict__ thr, int T) {
@@ -49,7 +46,7 @@ __device__ __forceinline__ int bucket_of_uniform(float p, const float* __restric
 // resolved against the batch-global decision by the caller). skip_done: rows
 // marked rowinv < 0 were binned by k_mc_onepass and are left out.
 // mode 0: multiclass one-vs-rest, mode 1: multilabel.
-template <typename T_, bool IS_BF16>
+template <typename T_>
 __device__ __forceinline__ void curve_hist_tile(
     const T_* __restrict__ probs, const long long* __restrict__ target, long long B, long long C,
     const float* __restrict__ sthr, int T, long long ignore_index, int has_ignore, int mode,
@@ -74,16 +71,7 @@ __device__ __forceinline__ void curve_hist_tile(
     // the latency bottleneck at small chunks)
     float pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     const bool vec4 = (c_hi - c_lo) == 4 && ((c_lo & 3) == 0) && ((C & 3) == 0);
-    if (valid && vec4) {
-        if (IS_BF16) {
-            ushort4 u = reinterpret_cast<const ushort4*>(prow)[c_lo >> 2];
-            pv[0] = bf16_to_f32(u.x); pv[1] = bf16_to_f32(u.y);
-            pv[2] = bf16_to_f32(u.z); pv[3] = bf16_to_f32(u.w);
-        } else {
-            float4 u = reinterpret_cast<const float4*>(prow)[c_lo >> 2];
-            pv[0] = u.x; pv[1] = u.y; pv[2] = u.z; pv[3] = u.w;
-        }
-    }
+    if (valid && vec4) unpack(reinterpret_cast<const vec4_t<T_>*>(prow)[c_lo >> 2], pv);
     for (ll c = c_lo; c < c_hi; c++) {
         int key = -1;
         if (valid) {
@@ -99,8 +87,7 @@ __device__ __forceinline__ void curve_hist_tile(
                 // selects, not pv[c - c_lo]: a runtime index would put pv in scratch
                 const int k = (int)(c - c_lo);
                 float p = vec4 ? (k == 0 ? pv[0] : k == 1 ? pv[1] : k == 2 ? pv[2] : pv[3])
-                               : (IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(prow)[c])
-                                          : (float)prow[c]);
+                               : ld_f32(prow, c);
                 if (norm == 1) p = expf(p - rmax) * rinv;
                 else if (norm == 2) p = 1.0f / (1.0f + expf(-p));
                 int j = uniform ? bucket_of_uniform(p, sthr, T, t0, inv_step)

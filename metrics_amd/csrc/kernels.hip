@@ -44,7 +44,7 @@ typedef long long ll;
 // one wave per row; tp/fp/fn per class via global atomics; optional confmat.
 // Tie-break matches torch.argmax: lowest index wins.
 // ---------------------------------------------------------------------------
-template <typename T, bool IS_BF16>
+template <typename T>
 __global__ void __launch_bounds__(256) k_mc_stat_logits(
     const T* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
     int has_ignore, unsigned long long* __restrict__ tp, unsigned long long* __restrict__ fp,
@@ -71,115 +71,55 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
         ll best_idx = 0x7fffffffffffffffLL;
         float sm_m = -3.4e38f, sm_s = 0.0f;  // online softmax (max, sumexp)
         unsigned int row_out = 0;
-        auto stats_fold = [&](const float* f, int k) {
-            if (!want_stats) return;
-            float m8 = f[0];
-            for (int i = 1; i < k; i++) m8 = fmaxf(m8, f[i]);
-            float s8 = 0.0f;
-            for (int i = 0; i < k; i++) {
-                row_out |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
-                s8 += __expf(f[i] - m8);
-            }
-            if (m8 > sm_m) { sm_s = sm_s * __expf(sm_m - m8) + s8; sm_m = m8; }
-            else { sm_s += s8 * __expf(m8 - sm_m); }
-        };
         // vectorized loads: 16B/lane for bf16 when C%8==0, else 8B/4B paths
-        if (IS_BF16 && (C & 7) == 0) {
-            struct U8 { ushort4 a; ushort4 b; };
-            const U8* pv = reinterpret_cast<const U8*>(prow);
+        if (is_bf16_v<T> && (C & 7) == 0) {
+            const bf16x8* pv = reinterpret_cast<const bf16x8*>(prow);
             const ll nvec = C / 8;
             for (ll v = lane; v < nvec; v += WAVE) {
-                U8 u = pv[v];
-                float f[8] = {bf16_to_f32(u.a.x), bf16_to_f32(u.a.y), bf16_to_f32(u.a.z), bf16_to_f32(u.a.w),
-                              bf16_to_f32(u.b.x), bf16_to_f32(u.b.y), bf16_to_f32(u.b.z), bf16_to_f32(u.b.w)};
-                ll c = v * 8;
-                stats_fold(f, 8);
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    if (f[k] > best || (f[k] == best && c + k < best_idx)) { best = f[k]; best_idx = c + k; }
-                }
+                float f[8];
+                unpack(pv[v], f);
+                if (want_stats) softmax_fold(f, sm_m, sm_s, row_out);
+                argmax_fold(f, v * 8, best, best_idx);
             }
         } else if ((C & 3) == 0) {
+            const vec4_t<T>* pv = reinterpret_cast<const vec4_t<T>*>(prow);
             const ll nvec = C / 4;
-            if (IS_BF16) {
-                const ushort4* pv = reinterpret_cast<const ushort4*>(prow);
-                for (ll v = lane; v < nvec; v += WAVE) {
-                    ushort4 u = pv[v];
-                    float f0 = bf16_to_f32(u.x), f1 = bf16_to_f32(u.y);
-                    float f2 = bf16_to_f32(u.z), f3 = bf16_to_f32(u.w);
-                    ll c = v * 4;
-                    float fv[4] = {f0, f1, f2, f3};
-                    stats_fold(fv, 4);
-                    if (f0 > best || (f0 == best && c < best_idx)) { best = f0; best_idx = c; }
-                    if (f1 > best || (f1 == best && c + 1 < best_idx)) { best = f1; best_idx = c + 1; }
-                    if (f2 > best || (f2 == best && c + 2 < best_idx)) { best = f2; best_idx = c + 2; }
-                    if (f3 > best || (f3 == best && c + 3 < best_idx)) { best = f3; best_idx = c + 3; }
-                }
-            } else {
-                const float4* pv = reinterpret_cast<const float4*>(prow);
-                for (ll v = lane; v < nvec; v += WAVE) {
-                    float4 u = pv[v];
-                    ll c = v * 4;
-                    float fv[4] = {u.x, u.y, u.z, u.w};
-                    stats_fold(fv, 4);
-                    if (u.x > best || (u.x == best && c < best_idx)) { best = u.x; best_idx = c; }
-                    if (u.y > best || (u.y == best && c + 1 < best_idx)) { best = u.y; best_idx = c + 1; }
-                    if (u.z > best || (u.z == best && c + 2 < best_idx)) { best = u.z; best_idx = c + 2; }
-                    if (u.w > best || (u.w == best && c + 3 < best_idx)) { best = u.w; best_idx = c + 3; }
-                }
+            for (ll v = lane; v < nvec; v += WAVE) {
+                float f[4];
+                unpack(pv[v], f);
+                if (want_stats) softmax_fold(f, sm_m, sm_s, row_out);
+                argmax_fold(f, v * 4, best, best_idx);
             }
         } else {
             for (ll c = lane; c < C; c += WAVE) {
-                float f = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(prow)[c])
-                                  : (float)prow[c];
-                stats_fold(&f, 1);
-                if (f > best || (f == best && c < best_idx)) { best = f; best_idx = c; }
+                const float f[1] = {ld_f32(prow, c)};
+                if (want_stats) softmax_fold(f, sm_m, sm_s, row_out);
+                argmax_fold(f, c, best, best_idx);
             }
         }
         if (want_stats) {
-            for (int off = WAVE / 2; off > 0; off >>= 1) {
-                float om = __shfl_down(sm_m, off);
-                float os = __shfl_down(sm_s, off);
-                if (om > sm_m) { sm_s = sm_s * __expf(sm_m - om) + os; sm_m = om; }
-                else { sm_s += os * __expf(om - sm_m); }
-            }
+            softmax_merge_wave(sm_m, sm_s);
             if (lane == 0) { rowmax[row] = sm_m; rowinv[row] = 1.0f / sm_s; }
         }
-        // wave shuffle reduce: max value, lowest index on tie
-        for (int off = WAVE / 2; off > 0; off >>= 1) {
-            float ov = __shfl_down(best, off);
-            ll oi = __shfl_down(best_idx, off);
-            if (ov > best || (ov == best && oi < best_idx)) { best = ov; best_idx = oi; }
-        }
+        argmax_merge_wave(best, best_idx);
         // the row's range bit lands in lane 0, which holds the target: an
         // ignored row takes no part in the softmax decision (reference order)
         const bool row_any_out = want_stats && __ballot(row_out != 0u) != 0ULL;
         if (lane == 0) {
-            ll t = target[row];
-            ll p = best_idx;
-            if (argmax_out) argmax_out[row] = p;
-            if (row_any_out && !(has_ignore && t == ignore_index)) outside = 1u;
-            // bounds guard: bad labels with validate_args=False must not corrupt memory
-            if (!(has_ignore && t == ignore_index) && t >= 0 && t < C && p >= 0 && p < C) {
-                my_valid++;
-                if (p == t) {
-                    atomicAdd(&tp[t], 1ULL);
-                } else {
-                    atomicAdd(&fp[p], 1ULL);
-                    atomicAdd(&fn[t], 1ULL);
-                }
-                if (confmat) atomicAdd(&confmat[t * C + p], 1ULL);
-            }
+            const ll t = target[row];
+            const bool ignored = has_ignore && t == ignore_index;
+            if (argmax_out) argmax_out[row] = best_idx;
+            if (row_any_out && !ignored) outside = 1u;
+            if (count_row(t, best_idx, C, ignored, tp, fp, fn, confmat)) my_valid++;
         }
     }
     // one valid-count atomic per block, not per row
     if (my_valid) atomicAdd(&block_valid, my_valid);
-    for (int off = WAVE / 2; off > 0; off >>= 1) outside |= __shfl_down(outside, off);
-    if (lane == 0 && outside) atomicOr(&blk_outside, 1u);
+    or_outside_block(outside, &blk_outside);
     __syncthreads();
     if (threadIdx.x == 0) {
         if (block_valid) atomicAdd(valid_count, (unsigned long long)block_valid);
-        if (E && blk_outside && E[0] != cur_epoch) atomicMax(&E[0], cur_epoch);
+        publish_outside(E, cur_epoch, blk_outside);
     }
 }
 
@@ -188,7 +128,7 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
 // THREAD walks one row serially (vector loads keep the per-wave footprint
 // contiguous: lane i streams row i, so a wave touches 64 consecutive rows =
 // full cachelines). No shuffles; per-row tail work is identical to K1.
-template <typename T, bool IS_BF16>
+template <typename T>
 __global__ void __launch_bounds__(256) k_mc_stat_logits_tiny(
     const T* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
     int has_ignore, unsigned long long* __restrict__ tp, unsigned long long* __restrict__ fp,
@@ -231,25 +171,15 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits_tiny(
                 else { sm_s += __expf(f - sm_m); }
             }
         };
-        if (IS_BF16 && (C & 3) == 0) {
-            const ushort4* pv = reinterpret_cast<const ushort4*>(prow);
+        if ((C & 3) == 0) {
+            const vec4_t<T>* pv = reinterpret_cast<const vec4_t<T>*>(prow);
             for (ll v = 0; v < C / 4; v++) {
-                ushort4 u = pv[v];
-                fold(bf16_to_f32(u.x), v * 4);
-                fold(bf16_to_f32(u.y), v * 4 + 1);
-                fold(bf16_to_f32(u.z), v * 4 + 2);
-                fold(bf16_to_f32(u.w), v * 4 + 3);
-            }
-        } else if (!IS_BF16 && (C & 3) == 0) {
-            const float4* pv = reinterpret_cast<const float4*>(prow);
-            for (ll v = 0; v < C / 4; v++) {
-                float4 u = pv[v];
-                fold(u.x, v * 4); fold(u.y, v * 4 + 1); fold(u.z, v * 4 + 2); fold(u.w, v * 4 + 3);
+                float f[4];
+                unpack(pv[v], f);
+                fold(f[0], v * 4); fold(f[1], v * 4 + 1); fold(f[2], v * 4 + 2); fold(f[3], v * 4 + 3);
             }
         } else {
-            for (ll c = 0; c < C; c++)
-                fold(IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(prow)[c])
-                             : (float)prow[c], c);
+            for (ll c = 0; c < C; c++) fold(ld_f32(prow, c), c);
         }
         if (want_stats) { rowmax[row] = sm_m; rowinv[row] = 1.0f / sm_s; }
         ll t = target[row];
@@ -283,7 +213,7 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits_tiny(
     }
     if (threadIdx.x == 0) {
         if (block_valid) atomicAdd(valid_count, (unsigned long long)block_valid);
-        if (E && blk_outside && E[0] != cur_epoch) atomicMax(&E[0], cur_epoch);
+        publish_outside(E, cur_epoch, blk_outside);
     }
 }
 
@@ -390,7 +320,7 @@ __global__ void __launch_bounds__(256) k_bincount_global(
 // out layout: [2][4] = {raw,sig} x {tp,fp,tn,fn}; flag: 1 if any value
 // outside [0,1].
 // ---------------------------------------------------------------------------
-template <typename T, bool IS_BF16>
+template <typename T>
 __global__ void __launch_bounds__(256) k_binary_stat(
     const T* __restrict__ preds, const ll* __restrict__ target, ll N, float threshold,
     ll ignore_index, int has_ignore, unsigned long long* __restrict__ out,
@@ -403,8 +333,7 @@ __global__ void __launch_bounds__(256) k_binary_stat(
     unsigned int outside = 0;
     for (; i < N; i += stride) {
         ll t = target[i];
-        float p = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(preds)[i])
-                          : (float)preds[i];
+        float p = ld_f32(preds, i);
         // the range test sees ignored elements too (reference: sigmoid iff ANY
         // element lies outside [0,1], decided before the ignore mask applies)
         outside |= (p < 0.0f || p > 1.0f) ? 1u : 0u;
@@ -428,15 +357,14 @@ __global__ void __launch_bounds__(256) k_binary_stat(
             for (int off = WAVE / 2; off > 0; off >>= 1) c += __shfl_down(c, off);
             if ((threadIdx.x & (WAVE - 1)) == 0 && c) atomicAdd(&blk[v * 4 + k], c);
         }
-    for (int off = WAVE / 2; off > 0; off >>= 1) outside |= __shfl_down(outside, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && outside) atomicOr(&blk_outside, 1u);
+    or_outside_block(outside, &blk_outside);
     __syncthreads();
     if (threadIdx.x < 8 && blk[threadIdx.x]) atomicAdd(&out[threadIdx.x], blk[threadIdx.x]);
     if (threadIdx.x == 0 && blk_outside) atomicOr(outside_flag, 1u);
 }
 
 // K4b: fused multilabel stat scores: (N, L) -> per-label [2][L][4] counters.
-template <typename T, bool IS_BF16>
+template <typename T>
 __global__ void __launch_bounds__(256) k_multilabel_stat(
     const T* __restrict__ preds, const ll* __restrict__ target, ll N, ll L, float threshold,
     ll ignore_index, int has_ignore, unsigned long long* __restrict__ out,
@@ -454,8 +382,7 @@ __global__ void __launch_bounds__(256) k_multilabel_stat(
     for (; i < N * L; i += stride) {
         ll l = i % L;
         ll t = target[i];
-        float p = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(preds)[i])
-                          : (float)preds[i];
+        float p = ld_f32(preds, i);
         // the range test sees ignored elements too (reference: sigmoid iff ANY
         // element lies outside [0,1], decided before the ignore mask applies)
         outside |= (p < 0.0f || p > 1.0f) ? 1u : 0u;
@@ -497,7 +424,7 @@ __global__ void __launch_bounds__(256) k_multilabel_stat(
 // has_ignore (binary curve only): samples whose target is ignore_index are
 // removed BEFORE the range test, as in the reference; the multilabel curve
 // tests every element and passes has_ignore = 0.
-template <typename T_, bool IS_BF16>
+template <typename T_>
 __global__ void __launch_bounds__(256) k_range_flag(
     const T_* __restrict__ x, ll N, const ll* __restrict__ target, ll ignore_index,
     int has_ignore, unsigned int* __restrict__ E) {
@@ -507,24 +434,20 @@ __global__ void __launch_bounds__(256) k_range_flag(
     unsigned int outside = 0;
     for (; i < N; i += stride) {
         if (has_ignore && target[i] == ignore_index) continue;
-        float p = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(x)[i])
-                          : (float)x[i];
+        float p = ld_f32(x, i);
         outside |= (p < 0.0f || p > 1.0f) ? 1u : 0u;
     }
     __shared__ unsigned int blk_outside;
     if (threadIdx.x == 0) blk_outside = 0;
     __syncthreads();
-    for (int off = WAVE / 2; off > 0; off >>= 1) outside |= __shfl_down(outside, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && outside) atomicOr(&blk_outside, 1u);
+    or_outside_block(outside, &blk_outside);
     __syncthreads();
-    // poll before the global atomic: once any block set the epoch, the rest
-    // skip — a per-wave atomicMax on one address serializes ~100ns each
-    if (threadIdx.x == 0 && blk_outside && E[0] != cur) atomicMax(&E[0], cur);
+    if (threadIdx.x == 0) publish_outside(E, cur, blk_outside);
 }
 
 // per-row max + 1/sum(exp(x - max)) for in-kernel softmax (online, one pass),
 // plus the outside-[0,1] flag. Wave per row, lanes stride classes (coalesced).
-template <typename T_, bool IS_BF16>
+template <typename T_>
 __global__ void __launch_bounds__(256) k_mc_rowstats(
     const T_* __restrict__ probs, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
     int has_ignore, unsigned int* __restrict__ E, float* __restrict__ rowmax,
@@ -545,62 +468,41 @@ __global__ void __launch_bounds__(256) k_mc_rowstats(
         // ignored samples before it); one wave-uniform load, only with has_ignore
         unsigned int row_out = 0;
         const bool row_ignored = has_ignore && target[row] == ignore_index;
-        auto fold8 = [&](const float* f, int k) {
-            float m8 = f[0];
-            for (int i = 1; i < k; i++) m8 = fmaxf(m8, f[i]);
-            float s8 = 0.0f;
-            for (int i = 0; i < k; i++) {
-                row_out |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
-                s8 += __expf(f[i] - m8);
-            }
-            if (m8 > m) { s = s * __expf(m - m8) + s8; m = m8; }
-            else { s += s8 * __expf(m8 - m); }
-        };
-        if (IS_BF16 && (C & 7) == 0) {
-            struct U8 { ushort4 a; ushort4 b; };
-            const U8* pv = reinterpret_cast<const U8*>(prow);
+        if (is_bf16_v<T_> && (C & 7) == 0) {
+            const bf16x8* pv = reinterpret_cast<const bf16x8*>(prow);
             const ll nvec = C / 8;
             for (ll v = lane; v < nvec; v += WAVE) {
-                U8 u = pv[v];
-                float f[8] = {bf16_to_f32(u.a.x), bf16_to_f32(u.a.y), bf16_to_f32(u.a.z),
-                              bf16_to_f32(u.a.w), bf16_to_f32(u.b.x), bf16_to_f32(u.b.y),
-                              bf16_to_f32(u.b.z), bf16_to_f32(u.b.w)};
-                fold8(f, 8);
+                float f[8];
+                unpack(pv[v], f);
+                softmax_fold(f, m, s, row_out);
             }
-        } else if (!IS_BF16 && (C & 3) == 0) {
-            const float4* pv = reinterpret_cast<const float4*>(prow);
+        } else if (!is_bf16_v<T_> && (C & 3) == 0) {
+            const vec4_t<T_>* pv = reinterpret_cast<const vec4_t<T_>*>(prow);
             const ll nvec = C / 4;
             for (ll v = lane; v < nvec; v += WAVE) {
-                float4 u = pv[v];
-                float f[4] = {u.x, u.y, u.z, u.w};
-                fold8(f, 4);
+                float f[4];
+                unpack(pv[v], f);
+                softmax_fold(f, m, s, row_out);
             }
         } else {
             for (ll c = lane; c < C; c += WAVE) {
-                float f = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(prow)[c])
-                                  : (float)prow[c];
-                fold8(&f, 1);
+                const float f[1] = {ld_f32(prow, c)};
+                softmax_fold(f, m, s, row_out);
             }
         }
-        for (int off = WAVE / 2; off > 0; off >>= 1) {
-            float om = __shfl_down(m, off);
-            float os = __shfl_down(s, off);
-            if (om > m) { s = s * __expf(m - om) + os; m = om; }
-            else { s += os * __expf(om - m); }
-        }
+        softmax_merge_wave(m, s);
         if (lane == 0) { rowmax[row] = m; rowinv[row] = 1.0f / s; }
         outside |= row_ignored ? 0u : row_out;
     }
     __shared__ unsigned int blk_outside2;
     if (threadIdx.x == 0) blk_outside2 = 0;
     __syncthreads();
-    for (int off = WAVE / 2; off > 0; off >>= 1) outside |= __shfl_down(outside, off);
-    if (lane == 0 && outside) atomicOr(&blk_outside2, 1u);
+    or_outside_block(outside, &blk_outside2);
     __syncthreads();
-    if (threadIdx.x == 0 && blk_outside2 && E[0] != cur) atomicMax(&E[0], cur);
+    if (threadIdx.x == 0) publish_outside(E, cur, blk_outside2);
 }
 
-template <typename T_, bool IS_BF16>
+template <typename T_>
 __global__ void __launch_bounds__(256) k_binary_curve_hist(
     const T_* __restrict__ preds, const ll* __restrict__ target, ll N,
     const float* __restrict__ thresholds, int T, ll ignore_index, int has_ignore,
@@ -617,8 +519,7 @@ __global__ void __launch_bounds__(256) k_binary_curve_hist(
     for (; i < N; i += stride) {
         ll t = target[i];
         if (has_ignore && t == ignore_index) continue;
-        float p = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(preds)[i])
-                          : (float)preds[i];
+        float p = ld_f32(preds, i);
         if (do_sigmoid) p = 1.0f / (1.0f + expf(-p));
         int j = uniform ? bucket_of_uniform(p, sthr, T, t0, inv_step) : bucket_of(p, sthr, T);
         atomicAdd(&lhist[j * 2 + (t == 1 ? 1 : 0)], 1u);
@@ -643,7 +544,7 @@ __global__ void __launch_bounds__(256) k_binary_curve_hist(
 // csrc/probe_curve.hip) by the wave's key-multiplicity. Per-lane row reads are
 // sequential in c => L1-resident after the first touch of each 64B line.
 // grid: x = class chunks, y = row chunks of 256.
-template <typename T_, bool IS_BF16>
+template <typename T_>
 __global__ void __launch_bounds__(256) k_multiclass_curve_hist(
     const T_* __restrict__ probs, const ll* __restrict__ target, ll B, ll C,
     const float* __restrict__ thresholds, int T, ll ignore_index, int has_ignore, int mode,
@@ -669,9 +570,9 @@ __global__ void __launch_bounds__(256) k_multiclass_curve_hist(
     const ll c_hi = min(c_lo + (ll)c_chunk, C);
     const int norm = (norm_kind && E && E[0] == E[1] + 1u) ? norm_kind : 0;
     // the tile body is shared with the one-pass tail kernel (curve_common.h)
-    curve_hist_tile<T_, IS_BF16>(probs, target, B, C, sthr2, T, ignore_index, has_ignore, mode,
-                                 uniform, t0, inv_step, c_lo, c_hi, (ll)blockIdx.y * 256, norm,
-                                 rowmax, rowinv, /*skip_done=*/false, hist);
+    curve_hist_tile<T_>(probs, target, B, C, sthr2, T, ignore_index, has_ignore, mode, uniform, t0,
+                        inv_step, c_lo, c_hi, (ll)blockIdx.y * 256, norm, rowmax, rowinv,
+                        /*skip_done=*/false, hist);
 }
 
 // LDS-privatized variant: each block owns a (class-chunk x T+1 x 2) uint32
@@ -680,7 +581,7 @@ __global__ void __launch_bounds__(256) k_multiclass_curve_hist(
 // the per-wave ballot-merge variant is atomic-bound (softmax skew piles most
 // of a class's mass into few buckets -> LDS same-address atomics are ~4x
 // cheaper than L2, and the flush is one atomic per NONZERO bin per block).
-template <typename T_, bool IS_BF16>
+template <typename T_>
 __global__ void __launch_bounds__(256) k_multiclass_curve_hist_lds(
     const T_* __restrict__ probs, const ll* __restrict__ target, ll B, ll C,
     const float* __restrict__ thresholds, int T, ll ignore_index, int has_ignore, int mode,
@@ -721,9 +622,7 @@ __global__ void __launch_bounds__(256) k_multiclass_curve_hist_lds(
                 if (has_ignore && t == ignore_index) label = -1;
             }
             if (label >= 0) {
-                float p = IS_BF16
-                              ? bf16_to_f32(reinterpret_cast<const unsigned short*>(probs)[row * C + c])
-                              : (float)probs[row * C + c];
+                float p = ld_f32(probs, row * C + c);
                 if (norm == 1) p = expf(p - rowmax[row]) * rowinv[row];
                 else if (norm == 2) p = 1.0f / (1.0f + expf(-p));
                 const int j = uniform ? bucket_of_uniform(p, sthr, T, t0, inv_step)
@@ -969,40 +868,8 @@ __global__ void k_epoch_bump(unsigned int* __restrict__ E) {
     if (threadIdx.x == 0) E[1] += 1u;
 }
 
-// ---------------------------------------------------------------------------
-// fused stat-delta apply: given the kernel scratch [tp|fp|fn|valid] produced
-// by k_mc_stat_*, add the deltas into the four metric state tensors
-// (tn += valid - tp - fp - fn). ONE launch replaces ~8 small torch kernels.
-__global__ void k_apply_stat_deltas(
-    unsigned long long* __restrict__ scratch /* 3*C + 1 */, ll C,
-    ll* __restrict__ tp, ll* __restrict__ fp, ll* __restrict__ tn, ll* __restrict__ fn,
-    unsigned int* __restrict__ E /* nullable: close the curve epoch here */) {
-    if (E && threadIdx.x == 0) E[1] += 1u;
-    // SINGLE block: every thread can read the valid slot before thread 0
-    // zeroes it (post-sync), so the whole scratch is consumed and re-zeroed
-    // in one launch with no cross-block race and no host-side epochs —
-    // which also makes the launch hipGraph-capturable.
-    __shared__ unsigned long long valid_s;
-    if (threadIdx.x == 0) valid_s = scratch[3 * C];
-    __syncthreads();
-    const ll valid = (ll)valid_s;
-    if (threadIdx.x == 0) scratch[3 * C] = 0;
-    for (ll i = threadIdx.x; i < C; i += blockDim.x) {
-        const ll dtp = (ll)scratch[i];
-        const ll dfp = (ll)scratch[C + i];
-        const ll dfn = (ll)scratch[2 * C + i];
-        scratch[i] = 0;  // same thread read it: safe in-flight zeroing
-        scratch[C + i] = 0;
-        scratch[2 * C + i] = 0;
-        tp[i] += dtp;
-        fp[i] += dfp;
-        fn[i] += dfn;
-        tn[i] += valid - dtp - dfp - dfn;
-    }
-}
-
 // exact-match epilogue: correct += sum(tp), total += valid — one block,
-// zeroes the scratch in-flight (same ping-pong valid protocol as apply_deltas).
+// zeroes the scratch in-flight (same valid-slot protocol as k_apply_stat_exact).
 __global__ void k_exact_apply(unsigned long long* __restrict__ scratch, ll C, ll B,
                               int zero_scratch, ll* __restrict__ correct, ll* __restrict__ total) {
     __shared__ unsigned long long part[256];
@@ -1031,13 +898,19 @@ __global__ void k_exact_apply(unsigned long long* __restrict__ scratch, ll C, ll
     }
 }
 
-// fused epilogue for the collection path: stat-delta apply + exact-match
-// accumulation in ONE single-block launch (replaces the back-to-back
-// k_exact_apply + k_apply_stat_deltas pair; saves a launch per step).
+// fused stat-delta apply: given the kernel scratch [tp|fp|fn|valid] produced
+// by k_mc_stat_*, add the deltas into the four metric state tensors
+// (tn += valid - tp - fp - fn) and, when correct/total are given, the
+// exact-match accumulation of k_exact_apply — ONE launch replaces ~8 small
+// torch kernels (and the back-to-back k_exact_apply + apply pair).
+// SINGLE block: every thread can read the valid slot before thread 0 zeroes
+// it (post-sync), so the whole scratch is consumed and re-zeroed in one launch
+// with no cross-block race and no host-side epochs — which also makes the
+// launch hipGraph-capturable.
 __global__ void k_apply_stat_exact(
     unsigned long long* __restrict__ scratch /* 3*C + 1 */, ll C, ll B,
     ll* __restrict__ tp, ll* __restrict__ fp, ll* __restrict__ tn, ll* __restrict__ fn,
-    ll* __restrict__ correct, ll* __restrict__ total,
+    ll* __restrict__ correct /* nullable, with total */, ll* __restrict__ total,
     unsigned int* __restrict__ E /* nullable: close the curve epoch here */) {
     if (E && threadIdx.x == 0) E[1] += 1u;
     __shared__ unsigned long long part[256];
@@ -1047,19 +920,9 @@ __global__ void k_apply_stat_exact(
     const ll valid = (ll)valid_s;
     if (threadIdx.x == 0) scratch[3 * C] = 0;
     unsigned long long acc = 0;
-    for (ll i = threadIdx.x; i < C; i += blockDim.x) {
-        const ll dtp = (ll)scratch[i];
-        const ll dfp = (ll)scratch[C + i];
-        const ll dfn = (ll)scratch[2 * C + i];
-        scratch[i] = 0;
-        scratch[C + i] = 0;
-        scratch[2 * C + i] = 0;
-        acc += (unsigned long long)dtp;
-        tp[i] += dtp;
-        fp[i] += dfp;
-        fn[i] += dfn;
-        tn[i] += valid - dtp - dfp - dfn;
-    }
+    for (ll i = threadIdx.x; i < C; i += blockDim.x)
+        acc += (unsigned long long)apply_stat_class(scratch, C, i, valid, tp, fp, tn, fn);
+    if (!correct) return;  // block-uniform
     part[threadIdx.x] = acc;
     __syncthreads();
     for (int off = 128; off > 0; off >>= 1) {
@@ -1151,15 +1014,6 @@ __device__ void _linear_stat_eval(
     }
 }
 
-__global__ void k_linear_stat_compute(
-    const ll* __restrict__ tp, const ll* __restrict__ fp, const ll* __restrict__ tn,
-    const ll* __restrict__ fn, ll C, float n0, float n1, float n2, float n3, float d0, float d1,
-    float d2, float d3, int avg_mode, int zero_w_topk, float zero_division, float post_a,
-    float post_b, float* __restrict__ out) {
-    _linear_stat_eval(tp, fp, tn, fn, C, n0, n1, n2, n3, d0, d1, d2, d3, avg_mode, zero_w_topk,
-                      zero_division, post_a, post_b, out);
-}
-
 // batched variant: one block per formula over the SAME shared (C,) stat
 // states — the 9 linear stat metrics of a compute group pay ONE dispatch per
 // compute generation instead of nine. params: 13 floats per formula
@@ -1235,7 +1089,7 @@ __global__ void k_curve_auc_from_confmat(
 //     (n. sum_x, sum_x2, sum_y, sum_y2, sum_xy -> 6 outputs), 5 = logcosh
 // partials: (num_blocks, n_out) f64; second kernel reduces in fixed order.
 // ---------------------------------------------------------------------------
-template <typename T, bool IS_BF16>
+template <typename T>
 __global__ void __launch_bounds__(256) k_err_reduce_partial(
     const T* __restrict__ x, const T* __restrict__ y, ll N, int op, double eps,
     double* __restrict__ partials, int n_out) {
@@ -1244,8 +1098,7 @@ __global__ void __launch_bounds__(256) k_err_reduce_partial(
     ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
     ll stride = (ll)gridDim.x * blockDim.x;
     for (; i < N; i += stride) {
-        float xf = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(x)[i]) : (float)x[i];
-        float yf = IS_BF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(y)[i]) : (float)y[i];
+        float xf = ld_f32(x, i), yf = ld_f32(y, i);
         double xd = xf, yd = yf;
         switch (op) {
             case 0: { double d = xd - yd; acc[0] += d * d; } break;
@@ -1355,6 +1208,11 @@ int ma_mc_stat_logits(uintptr_t stream, uintptr_t preds, int dtype /*0=f32 1=bf1
                       uintptr_t fp, uintptr_t fn, uintptr_t confmat, uintptr_t valid_count,
                       uintptr_t argmax_out, uintptr_t rowmax, uintptr_t rowinv, uintptr_t epoch_buf) {
     hipStream_t s = (hipStream_t)stream;
+#define MC_STAT_ARGS                                                                               \
+    (const DT*)preds, (const ll*)target, B, C, ignore_index, has_ignore, (unsigned long long*)tp,  \
+        (unsigned long long*)fp, (unsigned long long*)fn, (unsigned long long*)confmat,            \
+        (unsigned long long*)valid_count, (ll*)argmax_out, (float*)rowmax, (float*)rowinv,         \
+        (unsigned int*)epoch_buf
     // each wave loops several rows: more vector loads in flight per lane
     // (latency-bound otherwise; sweep tools/curve_sweep.py analogue)
     static int rows_div = 0;
@@ -1373,33 +1231,12 @@ int ma_mc_stat_logits(uintptr_t stream, uintptr_t preds, int dtype /*0=f32 1=bf1
         int grid = grid_for(B, 256);
         if (grid > 4096) grid = 4096;
         const size_t shmem = (size_t)(3 * C + (confmat && C <= 64 ? C * C : 0)) * sizeof(unsigned int);
-        if (dtype == 0)
-            k_mc_stat_logits_tiny<float, false><<<grid, 256, shmem, s>>>(
-                (const float*)preds, (const ll*)target, B, C, ignore_index, has_ignore,
-                (unsigned long long*)tp, (unsigned long long*)fp, (unsigned long long*)fn,
-                (unsigned long long*)confmat, (unsigned long long*)valid_count, (ll*)argmax_out,
-                (float*)rowmax, (float*)rowinv, (unsigned int*)epoch_buf);
-        else
-            k_mc_stat_logits_tiny<unsigned short, true><<<grid, 256, shmem, s>>>(
-                (const unsigned short*)preds, (const ll*)target, B, C, ignore_index, has_ignore,
-                (unsigned long long*)tp, (unsigned long long*)fp, (unsigned long long*)fn,
-                (unsigned long long*)confmat, (unsigned long long*)valid_count, (ll*)argmax_out,
-                (float*)rowmax, (float*)rowinv, (unsigned int*)epoch_buf);
+        LAUNCH_BY_DTYPE(dtype, k_mc_stat_logits_tiny, grid, 256, shmem, s, MC_STAT_ARGS);
         return (int)hipGetLastError();
     }
     int grid = grid_for(B, rows_div);
-    if (dtype == 0)
-        k_mc_stat_logits<float, false><<<grid, 256, 0, s>>>(
-            (const float*)preds, (const ll*)target, B, C, ignore_index, has_ignore,
-            (unsigned long long*)tp, (unsigned long long*)fp, (unsigned long long*)fn,
-            (unsigned long long*)confmat, (unsigned long long*)valid_count, (ll*)argmax_out,
-            (float*)rowmax, (float*)rowinv, (unsigned int*)epoch_buf);
-    else
-        k_mc_stat_logits<unsigned short, true><<<grid, 256, 0, s>>>(
-            (const unsigned short*)preds, (const ll*)target, B, C, ignore_index, has_ignore,
-            (unsigned long long*)tp, (unsigned long long*)fp, (unsigned long long*)fn,
-            (unsigned long long*)confmat, (unsigned long long*)valid_count, (ll*)argmax_out,
-            (float*)rowmax, (float*)rowinv, (unsigned int*)epoch_buf);
+    LAUNCH_BY_DTYPE(dtype, k_mc_stat_logits, grid, 256, 0, s, MC_STAT_ARGS);
+#undef MC_STAT_ARGS
     return (int)hipGetLastError();
 }
 
@@ -1435,14 +1272,9 @@ int ma_binary_stat(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t targe
                    float threshold, ll ignore_index, int has_ignore, uintptr_t out,
                    uintptr_t outside_flag) {
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0)
-        k_binary_stat<float, false><<<grid_for(N, 256), 256, 0, s>>>(
-            (const float*)preds, (const ll*)target, N, threshold, ignore_index, has_ignore,
-            (unsigned long long*)out, (unsigned int*)outside_flag);
-    else
-        k_binary_stat<unsigned short, true><<<grid_for(N, 256), 256, 0, s>>>(
-            (const unsigned short*)preds, (const ll*)target, N, threshold, ignore_index, has_ignore,
-            (unsigned long long*)out, (unsigned int*)outside_flag);
+    LAUNCH_BY_DTYPE(dtype, k_binary_stat, grid_for(N, 256), 256, 0, s, (const DT*)preds,
+                    (const ll*)target, N, threshold, ignore_index, has_ignore,
+                    (unsigned long long*)out, (unsigned int*)outside_flag);
     return (int)hipGetLastError();
 }
 
@@ -1454,14 +1286,9 @@ int ma_multilabel_stat(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t t
     const size_t shmem = use_lds ? (size_t)(8 * L) * sizeof(unsigned int) : 0;
     int grid = grid_for(N * L, 256);
     if (grid > 4096) grid = 4096;
-    if (dtype == 0)
-        k_multilabel_stat<float, false><<<grid, 256, shmem, s>>>(
-            (const float*)preds, (const ll*)target, N, L, threshold, ignore_index, has_ignore,
-            (unsigned long long*)out, (unsigned int*)outside_flag, use_lds);
-    else
-        k_multilabel_stat<unsigned short, true><<<grid, 256, shmem, s>>>(
-            (const unsigned short*)preds, (const ll*)target, N, L, threshold, ignore_index,
-            has_ignore, (unsigned long long*)out, (unsigned int*)outside_flag, use_lds);
+    LAUNCH_BY_DTYPE(dtype, k_multilabel_stat, grid, 256, shmem, s, (const DT*)preds,
+                    (const ll*)target, N, L, threshold, ignore_index, has_ignore,
+                    (unsigned long long*)out, (unsigned int*)outside_flag, use_lds);
     return (int)hipGetLastError();
 }
 
@@ -1472,34 +1299,21 @@ int ma_binary_curve_hist(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
     hipStream_t s = (hipStream_t)stream;
     size_t shmem = (size_t)(T + 1) * 2 * sizeof(unsigned int) + (size_t)T * sizeof(float);
     if (shmem > 160 * 1024) return -100;  // thresholds too large for LDS path
-    if (norm_sigmoid && flag) {
-        if (dtype == 0)
-            k_range_flag<float, false><<<grid_for(N, 256), 256, 0, s>>>(
-                (const float*)preds, N, (const ll*)target, ignore_index, has_ignore,
-                (unsigned int*)flag);
-        else
-            k_range_flag<unsigned short, true><<<grid_for(N, 256), 256, 0, s>>>(
-                (const unsigned short*)preds, N, (const ll*)target, ignore_index, has_ignore,
-                (unsigned int*)flag);
-    }
-    if (dtype == 0)
-        k_binary_curve_hist<float, false><<<grid_for(N, 256), 256, shmem, s>>>(
-            (const float*)preds, (const ll*)target, N, (const float*)thresholds, T, ignore_index,
-            has_ignore, uniform, t0, inv_step, norm_sigmoid, (const unsigned int*)flag,
-            (unsigned long long*)hist);
-    else
-        k_binary_curve_hist<unsigned short, true><<<grid_for(N, 256), 256, shmem, s>>>(
-            (const unsigned short*)preds, (const ll*)target, N, (const float*)thresholds, T,
-            ignore_index, has_ignore, uniform, t0, inv_step, norm_sigmoid, (const unsigned int*)flag,
-            (unsigned long long*)hist);
+    if (norm_sigmoid && flag)
+        LAUNCH_BY_DTYPE(dtype, k_range_flag, grid_for(N, 256), 256, 0, s, (const DT*)preds, N,
+                        (const ll*)target, ignore_index, has_ignore, (unsigned int*)flag);
+    LAUNCH_BY_DTYPE(dtype, k_binary_curve_hist, grid_for(N, 256), 256, shmem, s, (const DT*)preds,
+                    (const ll*)target, N, (const float*)thresholds, T, ignore_index, has_ignore,
+                    uniform, t0, inv_step, norm_sigmoid, (const unsigned int*)flag,
+                    (unsigned long long*)hist);
     return (int)hipGetLastError();
 }
 
-static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target, ll B,
-                              ll C, uintptr_t thresholds, int T, ll ignore_index, int has_ignore,
-                              int mode, int uniform, float t0, float inv_step, int norm_kind,
-                              uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv, int variant,
-                              int c_chunk_override, int stats_ready, uintptr_t hist) {
+int ma_multiclass_curve_hist(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target, ll B,
+                             ll C, uintptr_t thresholds, int T, ll ignore_index, int has_ignore,
+                             int mode, int uniform, float t0, float inv_step, int norm_kind,
+                             uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv, int variant,
+                             int c_chunk_override, int stats_ready, uintptr_t hist) {
     hipStream_t s = (hipStream_t)stream;
     size_t shmem = (size_t)T * sizeof(float);
     if (shmem > 160 * 1024) return -100;
@@ -1514,22 +1328,12 @@ static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uint
             if (rows_div < 4) rows_div = 4;
         }
         int grid = grid_for(B, rows_div);
-        if (dtype == 0)
-            k_mc_rowstats<float, false><<<grid, 256, 0, s>>>(
-                (const float*)probs, (const ll*)target, B, C, ignore_index,
-                has_ignore && mode == 0, (unsigned int*)flag, (float*)rowmax, (float*)rowinv);
-        else
-            k_mc_rowstats<unsigned short, true><<<grid, 256, 0, s>>>(
-                (const unsigned short*)probs, (const ll*)target, B, C, ignore_index,
-                has_ignore && mode == 0, (unsigned int*)flag, (float*)rowmax, (float*)rowinv);
+        LAUNCH_BY_DTYPE(dtype, k_mc_rowstats, grid, 256, 0, s, (const DT*)probs,
+                        (const ll*)target, B, C, ignore_index, has_ignore && mode == 0,
+                        (unsigned int*)flag, (float*)rowmax, (float*)rowinv);
     } else if (norm_kind == 2 && flag) {
-        if (dtype == 0)
-            k_range_flag<float, false><<<grid_for(B * C, 256), 256, 0, s>>>(
-                (const float*)probs, B * C, (const ll*)nullptr, 0, 0, (unsigned int*)flag);
-        else
-            k_range_flag<unsigned short, true><<<grid_for(B * C, 256), 256, 0, s>>>(
-                (const unsigned short*)probs, B * C, (const ll*)nullptr, 0, 0,
-                (unsigned int*)flag);
+        LAUNCH_BY_DTYPE(dtype, k_range_flag, grid_for(B * C, 256), 256, 0, s, (const DT*)probs,
+                        B * C, (const ll*)nullptr, 0, 0, (unsigned int*)flag);
     }
     // LDS-privatized variant when the per-block histogram fits comfortably
     // the kernel maps 32 threads to the classes of a chunk: a wider chunk would
@@ -1549,18 +1353,11 @@ static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uint
         if (row_chunks_l > max_rc) row_chunks_l = max_rc;
         int rows_per_block = (int)((B + row_chunks_l - 1) / row_chunks_l);
         dim3 gridl((unsigned)c_chunks_l, (unsigned)row_chunks_l);
-        if (dtype == 0)
-            k_multiclass_curve_hist_lds<float, false><<<gridl, 256, lds_bytes, s>>>(
-                (const float*)probs, (const ll*)target, B, C, (const float*)thresholds, T,
-                ignore_index, has_ignore, mode, uniform, t0, inv_step, lds_c_chunk,
-                rows_per_block, norm_kind, (const unsigned int*)flag, (const float*)rowmax,
-                (const float*)rowinv, (unsigned long long*)hist);
-        else
-            k_multiclass_curve_hist_lds<unsigned short, true><<<gridl, 256, lds_bytes, s>>>(
-                (const unsigned short*)probs, (const ll*)target, B, C, (const float*)thresholds,
-                T, ignore_index, has_ignore, mode, uniform, t0, inv_step, lds_c_chunk,
-                rows_per_block, norm_kind, (const unsigned int*)flag, (const float*)rowmax,
-                (const float*)rowinv, (unsigned long long*)hist);
+        LAUNCH_BY_DTYPE(dtype, k_multiclass_curve_hist_lds, gridl, 256, lds_bytes, s,
+                        (const DT*)probs, (const ll*)target, B, C, (const float*)thresholds, T,
+                        ignore_index, has_ignore, mode, uniform, t0, inv_step, lds_c_chunk,
+                        rows_per_block, norm_kind, (const unsigned int*)flag,
+                        (const float*)rowmax, (const float*)rowinv, (unsigned long long*)hist);
         return (int)hipGetLastError();
     }
     ll row_chunks = (B + 255) / 256;
@@ -1572,29 +1369,11 @@ static int mc_curve_hist_impl(uintptr_t stream, uintptr_t probs, int dtype, uint
     ll c_chunks = (C + c_chunk - 1) / c_chunk;
     if (row_chunks > 65535 || c_chunks > 2147483647LL) return -101;
     dim3 grid((unsigned)c_chunks, (unsigned)row_chunks);
-    if (dtype == 0)
-        k_multiclass_curve_hist<float, false><<<grid, 256, shmem, s>>>(
-            (const float*)probs, (const ll*)target, B, C, (const float*)thresholds, T, ignore_index,
-            has_ignore, mode, uniform, t0, inv_step, c_chunk, norm_kind,
-            (const unsigned int*)flag, (const float*)rowmax, (const float*)rowinv,
-            (unsigned long long*)hist);
-    else
-        k_multiclass_curve_hist<unsigned short, true><<<grid, 256, shmem, s>>>(
-            (const unsigned short*)probs, (const ll*)target, B, C, (const float*)thresholds, T,
-            ignore_index, has_ignore, mode, uniform, t0, inv_step, c_chunk, norm_kind,
-            (const unsigned int*)flag, (const float*)rowmax, (const float*)rowinv,
-            (unsigned long long*)hist);
+    LAUNCH_BY_DTYPE(dtype, k_multiclass_curve_hist, grid, 256, shmem, s, (const DT*)probs,
+                    (const ll*)target, B, C, (const float*)thresholds, T, ignore_index, has_ignore,
+                    mode, uniform, t0, inv_step, c_chunk, norm_kind, (const unsigned int*)flag,
+                    (const float*)rowmax, (const float*)rowinv, (unsigned long long*)hist);
     return (int)hipGetLastError();
-}
-
-int ma_multiclass_curve_hist(uintptr_t stream, uintptr_t probs, int dtype, uintptr_t target, ll B,
-                             ll C, uintptr_t thresholds, int T, ll ignore_index, int has_ignore,
-                             int mode, int uniform, float t0, float inv_step, int norm_kind,
-                             uintptr_t flag, uintptr_t rowmax, uintptr_t rowinv, int variant,
-                             int c_chunk_override, int stats_ready, uintptr_t hist) {
-    return mc_curve_hist_impl(stream, probs, dtype, target, B, C, thresholds, T, ignore_index,
-                              has_ignore, mode, uniform, t0, inv_step, norm_kind, flag, rowmax,
-                              rowinv, variant, c_chunk_override, stats_ready, hist);
 }
 
 int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int transposed,
@@ -1670,21 +1449,9 @@ int ma_curve_epoch_bump(uintptr_t stream, uintptr_t epoch_buf) {
 int ma_apply_stat_deltas(uintptr_t stream, uintptr_t scratch, ll C, uintptr_t tp,
                          uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t epoch_buf) {
     hipStream_t s = (hipStream_t)stream;
-    k_apply_stat_deltas<<<1, 256, 0, s>>>(
-        (unsigned long long*)scratch, C, (ll*)tp, (ll*)fp, (ll*)tn, (ll*)fn,
-        (unsigned int*)epoch_buf);
-    return (int)hipGetLastError();
-}
-
-int ma_linear_stat_compute(uintptr_t stream, uintptr_t tp, uintptr_t fp, uintptr_t tn,
-                           uintptr_t fn, ll C, float n0, float n1, float n2, float n3, float d0,
-                           float d1, float d2, float d3, int avg_mode, int zero_w_topk,
-                           float zero_division, float post_a, float post_b, uintptr_t out) {
-    hipStream_t s = (hipStream_t)stream;
-    k_linear_stat_compute<<<1, 256, 0, s>>>((const ll*)tp, (const ll*)fp, (const ll*)tn,
-                                            (const ll*)fn, C, n0, n1, n2, n3, d0, d1, d2, d3,
-                                            avg_mode, zero_w_topk, zero_division, post_a, post_b,
-                                            (float*)out);
+    k_apply_stat_exact<<<1, 256, 0, s>>>((unsigned long long*)scratch, C, 0, (ll*)tp, (ll*)fp,
+                                         (ll*)tn, (ll*)fn, nullptr, nullptr,
+                                         (unsigned int*)epoch_buf);
     return (int)hipGetLastError();
 }
 
@@ -1717,13 +1484,8 @@ int ma_exact_apply(uintptr_t stream, uintptr_t scratch, ll C, ll B, int zero_scr
 int ma_err_reduce(uintptr_t stream, uintptr_t x, uintptr_t y, int dtype, ll N, int op, double eps,
                   uintptr_t partials, int num_blocks, int n_out, uintptr_t out) {
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0)
-        k_err_reduce_partial<float, false><<<num_blocks, 256, 0, s>>>(
-            (const float*)x, (const float*)y, N, op, eps, (double*)partials, n_out);
-    else
-        k_err_reduce_partial<unsigned short, true><<<num_blocks, 256, 0, s>>>(
-            (const unsigned short*)x, (const unsigned short*)y, N, op, eps, (double*)partials,
-            n_out);
+    LAUNCH_BY_DTYPE(dtype, k_err_reduce_partial, num_blocks, 256, 0, s, (const DT*)x,
+                    (const DT*)y, N, op, eps, (double*)partials, n_out);
     k_err_reduce_final<<<1, 64, 0, s>>>((const double*)partials, num_blocks, n_out, (double*)out);
     return (int)hipGetLastError();
 }

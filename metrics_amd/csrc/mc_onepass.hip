@@ -8,8 +8,11 @@
 // registers (16 B per lane per vector, NV vectors per lane), so the row is
 // read from HBM once:
 //
-//  phase A  exactly k_mc_stat_logits: same fold order, same shuffle tree, so
-//           rowmax/rowinv are bit-identical to the two-kernel path.
+//  phase A  what k_mc_stat_logits does, through the same functions: both call
+//           softmax_fold / softmax_merge_wave, argmax_fold / argmax_merge_wave
+//           and count_row of row_fold.h (8-wide groups for bf16, 4-wide for
+//           fp32), so rowmax/rowinv and every count are bit-identical to the
+//           two-kernel path by construction.
 //  phase B  CERTAINTY RULE: if this row itself holds an element outside
 //           [0,1], the batch-global answer is already known to be "softmax",
 //           and the row is binned from registers right away. A row with every
@@ -46,6 +49,7 @@
 #include <stdlib.h>
 
 #include "curve_common.h"
+#include "row_fold.h"
 
 #define WAVE 64
 
@@ -67,7 +71,7 @@ typedef unsigned long long ull;
 #define ONEPASS_CS_WORDS(C) (ONEPASS_REC_OFF(C) + 2 * ONEPASS_GRID_MAX)
 #define ONEPASS_TAIL_GRID_DEFAULT 4096  // blocks of k_onepass_tail, see ma_mc_onepass_update
 
-template <bool IS_BF16, int NV>
+template <typename T_, int NV>
 __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_onepass(
     const uint4* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
     int has_ignore, ull* __restrict__ tp, ull* __restrict__ fp, ull* __restrict__ fn,
@@ -75,7 +79,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     const float* __restrict__ thresholds, int T, int uniform, float t0, float inv_step,
     ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cs /* [P|N1|N0 copies] */,
     uint4* __restrict__ records /* gridDim.x */) {
-    constexpr int EPV = IS_BF16 ? 8 : 4;  // elements per 16-byte vector
+    constexpr int EPV = 16 / sizeof(T_);  // elements per 16-byte vector
     extern __shared__ float sthr[];
     __shared__ unsigned int block_valid, blk_outside, blk_binned, blk_deferred, blk_correct;
 
@@ -91,18 +95,6 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     ull* __restrict__ cN0 = cs + (2 + (blockIdx.x & (ONEPASS_NCOPY - 1))) * C;
     unsigned int outside = 0;
     unsigned int my_valid = 0, my_binned = 0, my_deferred = 0, my_correct = 0;
-
-    auto unpack = [](const uint4& u, float* f) {
-        if (IS_BF16) {
-            f[0] = bf16_to_f32((unsigned short)(u.x & 0xffffu)); f[1] = bf16_to_f32((unsigned short)(u.x >> 16));
-            f[2] = bf16_to_f32((unsigned short)(u.y & 0xffffu)); f[3] = bf16_to_f32((unsigned short)(u.y >> 16));
-            f[4] = bf16_to_f32((unsigned short)(u.z & 0xffffu)); f[5] = bf16_to_f32((unsigned short)(u.z >> 16));
-            f[6] = bf16_to_f32((unsigned short)(u.w & 0xffffu)); f[7] = bf16_to_f32((unsigned short)(u.w >> 16));
-        } else {
-            f[0] = __uint_as_float(u.x); f[1] = __uint_as_float(u.y);
-            f[2] = __uint_as_float(u.z); f[3] = __uint_as_float(u.w);
-        }
-    };
 
     // the whole row, packed, in registers: vector k of this lane is pv[lane + 64*k]
     uint4 r[NV];
@@ -126,7 +118,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     while (row < B) {
         const ll t = target[row];
 
-        // ---- phase A: k_mc_stat_logits, same fold and tie-break ----
+        // ---- phase A: the folds of k_mc_stat_logits (row_fold.h) ----
         float best = -INFINITY;
         int best_idx = 0x7fffffff;
         float sm_m = -3.4e38f, sm_s = 0.0f;  // online softmax (max, sumexp)
@@ -136,23 +128,9 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             const int v = lane + k * WAVE;
             if (v < nvec) {
                 float f[EPV];
-                unpack(r[k], f);
-                float m8 = f[0];
-#pragma unroll
-                for (int i = 1; i < EPV; i++) m8 = fmaxf(m8, f[i]);
-                float s8 = 0.0f;
-#pragma unroll
-                for (int i = 0; i < EPV; i++) {
-                    row_out |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
-                    s8 += __expf(f[i] - m8);
-                }
-                if (m8 > sm_m) { sm_s = sm_s * __expf(sm_m - m8) + s8; sm_m = m8; }
-                else { sm_s += s8 * __expf(m8 - sm_m); }
-                const int c = v * EPV;
-#pragma unroll
-                for (int i = 0; i < EPV; i++) {
-                    if (f[i] > best || (f[i] == best && c + i < best_idx)) { best = f[i]; best_idx = c + i; }
-                }
+                unpack16<T_>(r[k], f);
+                softmax_fold(f, sm_m, sm_s, row_out);
+                argmax_fold(f, v * EPV, best, best_idx);
             }
         }
         // an ignored row takes no part in the softmax decision (the reference
@@ -160,17 +138,8 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         const bool ignored = has_ignore && t == ignore_index;
         if (ignored) row_out = 0u;
         outside |= row_out;
-        for (int off = WAVE / 2; off > 0; off >>= 1) {
-            float om = __shfl_down(sm_m, off);
-            float os = __shfl_down(sm_s, off);
-            if (om > sm_m) { sm_s = sm_s * __expf(sm_m - om) + os; sm_m = om; }
-            else { sm_s += os * __expf(om - sm_m); }
-        }
-        for (int off = WAVE / 2; off > 0; off >>= 1) {
-            float ov = __shfl_down(best, off);
-            int oi = __shfl_down(best_idx, off);
-            if (ov > best || (ov == best && oi < best_idx)) { best = ov; best_idx = oi; }
-        }
+        softmax_merge_wave(sm_m, sm_s);
+        argmax_merge_wave(best, best_idx);
         // lane 0 holds the row's (max, sumexp); every lane needs them for phase B
         const float rmax = __shfl(sm_m, 0);
         const float rinv = __shfl(1.0f / sm_s, 0);
@@ -178,17 +147,9 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         const bool bin_now = certain && !ignored;
         if (lane == 0) {
             const ll p = best_idx;
-            // bounds guard: bad labels with validate_args=False must not corrupt memory
-            if (!ignored && t >= 0 && t < C && p >= 0 && p < C) {
+            if (count_row(t, p, C, ignored, tp, fp, fn, confmat)) {
                 my_valid++;
-                if (p == t) {
-                    my_correct++;
-                    atomicAdd(&tp[t], 1ULL);
-                } else {
-                    atomicAdd(&fp[p], 1ULL);
-                    atomicAdd(&fn[t], 1ULL);
-                }
-                if (confmat) atomicAdd(&confmat[t * C + p], 1ULL);
+                if (p == t) my_correct++;
             }
             rowmax[row] = rmax;
             rowinv[row] = (bin_now || ignored) ? -rinv : rinv;
@@ -229,7 +190,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             for (int k = 0; k < NV; k++) {
                 if (lane + k * WAVE < nvec) {
                     float f[EPV];
-                    unpack(r[k], f);
+                    unpack16<T_>(r[k], f);
 #pragma unroll
                     for (int i = 0; i < EPV; i++)
                         todo |= (f[i] - rmax < dcut) ? 0ULL : (1ULL << (k * EPV + i));
@@ -241,7 +202,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
                 if (todo != 0ULL) {
                     const int e = __ffsll(todo) - 1;
                     todo &= todo - 1ULL;
-                    const int wi = IS_BF16 ? (e >> 1) : e;  // 32-bit word of the row slice
+                    const int wi = is_bf16_v<T_> ? (e >> 1) : e;  // 32-bit word of the row slice
                     unsigned int w = r[0].x;
 #pragma unroll
                     for (int q = 1; q < 4 * NV; q++) {
@@ -251,7 +212,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
                                                                : r[q >> 2].w;
                         w = (wi == q) ? cand : w;
                     }
-                    const float x = IS_BF16 ? __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16))
+                    const float x = is_bf16_v<T_> ? __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16))
                                             : __uint_as_float(w);
                     const int k = e / EPV, i = e % EPV;
                     bin_one(x, (lane + k * WAVE) * EPV + i);
@@ -266,8 +227,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     if (my_binned) atomicAdd(&blk_binned, my_binned);
     if (my_deferred) atomicAdd(&blk_deferred, my_deferred);
     if (my_correct) atomicAdd(&blk_correct, my_correct);
-    for (int off = WAVE / 2; off > 0; off >>= 1) outside |= __shfl_down(outside, off);
-    if (lane == 0 && outside) atomicOr(&blk_outside, 1u);
+    or_outside_block(outside, &blk_outside);
     __syncthreads();
     if (threadIdx.x == 0) {
         // one 16-byte store; a block holds < 2^31 rows, so bit 31 is free
@@ -290,7 +250,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
 //      over the (class-chunk, 256-row) tiles of the deferred pass.
 // Nothing written by one block is read by another; there is no ticket, spin
 // or grid-wide wait.
-template <typename T_, bool IS_BF16>
+template <typename T_>
 __global__ void __launch_bounds__(256) k_onepass_tail(
     const uint4* __restrict__ records, int grid /* blocks k_mc_onepass ran with */,
     ull* __restrict__ scratch /* 3*C + 1 */, ll C, ll B, ll* __restrict__ tp, ll* __restrict__ fp,
@@ -339,16 +299,7 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     // ---- (b) epilogue for one class ----
     const ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < C) {
-        const ll dtp = (ll)scratch[i];
-        const ll dfp = (ll)scratch[C + i];
-        const ll dfn = (ll)scratch[2 * C + i];
-        scratch[i] = 0;
-        scratch[C + i] = 0;
-        scratch[2 * C + i] = 0;
-        tp[i] += dtp;
-        fp[i] += dfp;
-        fn[i] += dfn;
-        tn[i] += valid - dtp - dfp - dfn;
+        apply_stat_class(scratch, C, i, valid, tp, fp, tn, fn);
         if (binned) {  // no row binned => the three counters are already zero
             const int b0 = bucket_of(0.0f, sthr_t, T);
             const ll P = (ll)cs[i];
@@ -401,9 +352,9 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
         }
         const ll c_lo = chunk * c_chunk;
         const ll c_hi = min(c_lo + (ll)c_chunk, C);
-        curve_hist_tile<T_, IS_BF16>(probs, target, B, C, sthr_t, T, ignore_index, has_ignore,
-                                     /*mode=*/0, uniform, t0, inv_step, c_lo, c_hi, ry * 256, norm,
-                                     rowmax, rowinv, /*skip_done=*/true, hist);
+        curve_hist_tile<T_>(probs, target, B, C, sthr_t, T, ignore_index, has_ignore, /*mode=*/0,
+                            uniform, t0, inv_step, c_lo, c_hi, ry * 256, norm, rowmax, rowinv,
+                            /*skip_done=*/true, hist);
     }
 }
 
@@ -428,18 +379,18 @@ int ma_mc_onepass_nv(int dtype /*0=f32 1=bf16*/, ll C, int T) {
 // u64 words of the curve scratch for C classes (records region included)
 int ma_mc_onepass_scratch_words(ll C) { return (int)ONEPASS_CS_WORDS(C); }
 
-#define ONEPASS_LAUNCH(BF, NV_)                                                                  \
-    k_mc_onepass<BF, NV_><<<grid, 256, shmem, s>>>(                                              \
+#define ONEPASS_LAUNCH(DT_, NV_)                                                                 \
+    k_mc_onepass<DT_, NV_><<<grid, 256, shmem, s>>>(                                             \
         (const uint4*)preds, (const ll*)target, B, C, ignore_index, has_ignore, sc, sc + C,      \
         sc + 2 * C, (ull*)confmat, (float*)rowmax, (float*)rowinv, (const float*)thresholds, T,  \
         uniform, t0, inv_step, (ull*)hist, (ull*)cscratch, records)
-
-#define ONEPASS_TAIL_LAUNCH(T_, BF)                                                              \
-    k_onepass_tail<T_, BF><<<tgrid, 256, shmem, s>>>(                                            \
-        records, grid, (ull*)scratch, C, B, (ll*)tp, (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct,    \
-        (ll*)total, (unsigned int*)epoch_buf, (ull*)cscratch, (const float*)thresholds, T,       \
-        (ull*)hist, (const T_*)preds, (const ll*)target, ignore_index, has_ignore, uniform, t0,  \
-        inv_step, c_chunk, (const float*)rowmax, (const float*)rowinv)
+#define ONEPASS_LAUNCH_NV(DT_)                                                                   \
+    do {                                                                                         \
+        if (nv == 1) ONEPASS_LAUNCH(DT_, 1);                                                     \
+        else if (nv == 2) ONEPASS_LAUNCH(DT_, 2);                                                \
+        else if (nv == 4) ONEPASS_LAUNCH(DT_, 4);                                                \
+        else ONEPASS_LAUNCH(DT_, 8);                                                             \
+    } while (0)
 
 // blocks of k_mc_onepass for B rows: one row per wave and pass, 4 waves per
 // block. Measured at B=8192 C=1000 (sweep knob MA_ONEPASS_GRID): 2048 blocks —
@@ -484,17 +435,8 @@ int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
     const int grid = B > 0 ? onepass_grid(B) : 0;
     if (B > 0) {
         ull* sc = (ull*)scratch;
-        if (dtype == 1) {
-            if (nv == 1) ONEPASS_LAUNCH(true, 1);
-            else if (nv == 2) ONEPASS_LAUNCH(true, 2);
-            else if (nv == 4) ONEPASS_LAUNCH(true, 4);
-            else ONEPASS_LAUNCH(true, 8);
-        } else {
-            if (nv == 1) ONEPASS_LAUNCH(false, 1);
-            else if (nv == 2) ONEPASS_LAUNCH(false, 2);
-            else if (nv == 4) ONEPASS_LAUNCH(false, 4);
-            else ONEPASS_LAUNCH(false, 8);
-        }
+        if (dtype == 0) ONEPASS_LAUNCH_NV(float);
+        else ONEPASS_LAUNCH_NV(unsigned short);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -523,8 +465,11 @@ int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
     const ll eblocks = (C + 255) / 256;
     if (tg < eblocks) tg = eblocks;
     const int tgrid = (int)((tg + 7) / 8 * 8);  // multiple of 8: block % 8 is the XCD
-    if (dtype == 1) ONEPASS_TAIL_LAUNCH(unsigned short, true);
-    else ONEPASS_TAIL_LAUNCH(float, false);
+    LAUNCH_BY_DTYPE(dtype, k_onepass_tail, tgrid, 256, shmem, s, records, grid, (ull*)scratch, C, B,
+                    (ll*)tp, (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct, (ll*)total,
+                    (unsigned int*)epoch_buf, (ull*)cscratch, (const float*)thresholds, T,
+                    (ull*)hist, (const DT*)preds, (const ll*)target, ignore_index, has_ignore,
+                    uniform, t0, inv_step, c_chunk, (const float*)rowmax, (const float*)rowinv);
     return (int)hipGetLastError();
 }
 

@@ -64,7 +64,6 @@ _SIGNATURES = {
     "ma_mc_onepass_update": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64],
     "ma_apply_stat_exact": [_U64, _U64, _LL, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
     "ma_curve_auc_from_confmat": [_U64, _U64, _I, _LL, _I, _U64, _U64],
-    "ma_linear_stat_compute": [_U64, _U64, _U64, _U64, _U64, _LL, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _F, _F, _F, _U64],
     "ma_err_reduce": [_U64, _U64, _U64, _I, _LL, _I, _D, _U64, _I, _I, _U64],
     "ma_box_iou": [_U64, _U64, _LL, _U64, _LL, _I, _U64],
     "ma_clf_curve_scratch_bytes": [_LL, _I, ctypes.POINTER(ctypes.c_ulonglong)],
@@ -137,6 +136,65 @@ def _to_supported(t: Tensor) -> Tensor:
     return t
 
 
+def _launch_mc_stat(
+    preds: Tensor, target: Tensor, C: int, ignore_index: Optional[int],
+    tp_ptr: int, fp_ptr: int, fn_ptr: int, confmat_ptr: int, valid_ptr: int,
+    argmax_ptr: int = 0, rowstats=None,
+) -> int:
+    """The one stat launch every multiclass update shares: ``ma_mc_stat_logits``
+    for (B, C) float ``preds`` (fused row-argmax), ``ma_mc_stat_labels`` for
+    integer label ``preds``. Counts land in the (C,) u64 buffers behind the
+    pointers (``confmat_ptr``/``argmax_ptr`` may be 0); ``rowstats`` =
+    (rowmax, rowinv, epoch_buf) also emits the softmax row statistics (logits
+    only). Returns B, the number of samples."""
+    lib = _lib()
+    ign = (ignore_index if ignore_index is not None else 0, 1 if ignore_index is not None else 0)
+    if preds.ndim == 2 and preds.is_floating_point():
+        preds = _to_supported(preds).contiguous()
+        target = target.contiguous().long()
+        B = preds.shape[0]
+        assert preds.shape[1] == C, "preds must be (B, num_classes)"
+        rs = [t.data_ptr() for t in rowstats] if rowstats is not None else [0, 0, 0]
+        rc = lib.ma_mc_stat_logits(
+            _stream(), preds.data_ptr(), _dtype_code(preds), target.data_ptr(), B, C, *ign,
+            tp_ptr, fp_ptr, fn_ptr, confmat_ptr, valid_ptr, argmax_ptr, *rs,
+        )
+        _check(rc, "ma_mc_stat_logits")
+    else:
+        preds = preds.contiguous().long().flatten()
+        target = target.contiguous().long().flatten()
+        B = preds.numel()
+        rc = lib.ma_mc_stat_labels(
+            _stream(), preds.data_ptr(), target.data_ptr(), B, C, *ign,
+            tp_ptr, fp_ptr, fn_ptr, confmat_ptr, valid_ptr,
+        )
+        _check(rc, "ma_mc_stat_labels")
+    return B
+
+
+def _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch: Tensor, confmat_ptr=0, rowstats=None) -> int:
+    """:func:`_launch_mc_stat` into a (3*C+1,) int64 scratch laid out [tp|fp|fn|valid]."""
+    p = scratch.data_ptr()
+    return _launch_mc_stat(preds, target, C, ignore_index, p, p + 8 * C, p + 16 * C, confmat_ptr,
+                           p + 24 * C, rowstats=rowstats)
+
+
+def _fresh_mc_stat(preds, target, C, ignore_index, want_confmat, argmax: Optional[Tensor] = None):
+    """:func:`_launch_mc_stat` into freshly zeroed per-class tensors."""
+    dev = preds.device
+    tp = torch.zeros(C, dtype=torch.long, device=dev)
+    fp = torch.zeros(C, dtype=torch.long, device=dev)
+    fn = torch.zeros(C, dtype=torch.long, device=dev)
+    valid = torch.zeros(1, dtype=torch.long, device=dev)
+    confmat = torch.zeros(C, C, dtype=torch.long, device=dev) if want_confmat else None
+    _launch_mc_stat(
+        preds, target, C, ignore_index, tp.data_ptr(), fp.data_ptr(), fn.data_ptr(),
+        confmat.data_ptr() if confmat is not None else 0, valid.data_ptr(),
+        argmax.data_ptr() if argmax is not None else 0,
+    )
+    return tp, fp, fn, valid, confmat
+
+
 def mc_stat_logits(
     preds: Tensor, target: Tensor, ignore_index: Optional[int], want_confmat: bool,
     want_argmax: bool = False,
@@ -145,69 +203,18 @@ def mc_stat_logits(
 
     Returns (tp, fp, fn, valid_count, confmat|None, argmax|None), all int64 on device.
     """
-    lib = _lib()
     assert preds.ndim == 2 and target.ndim == 1 and preds.shape[0] == target.shape[0]
-    preds = _to_supported(preds).contiguous()
-    target = target.contiguous().long()
+    assert preds.is_floating_point(), "integer preds are labels: use mc_stat_labels"
     B, C = preds.shape
-    dev = preds.device
-    tp = torch.zeros(C, dtype=torch.long, device=dev)
-    fp = torch.zeros(C, dtype=torch.long, device=dev)
-    fn = torch.zeros(C, dtype=torch.long, device=dev)
-    valid = torch.zeros(1, dtype=torch.long, device=dev)
-    confmat = torch.zeros(C, C, dtype=torch.long, device=dev) if want_confmat else None
-    argmax = torch.empty(B, dtype=torch.long, device=dev) if want_argmax else None
-    rc = lib.ma_mc_stat_logits(
-        _stream(),
-        preds.data_ptr(),
-        _dtype_code(preds),
-        target.data_ptr(),
-        B,
-        C,
-        ignore_index if ignore_index is not None else 0,
-        1 if ignore_index is not None else 0,
-        tp.data_ptr(),
-        fp.data_ptr(),
-        fn.data_ptr(),
-        confmat.data_ptr() if confmat is not None else 0,
-        valid.data_ptr(),
-        argmax.data_ptr() if argmax is not None else 0,
-        0, 0, 0,
-    )
-    _check(rc, "ma_mc_stat_logits")
-    return tp, fp, fn, valid, confmat, argmax
+    argmax = torch.empty(B, dtype=torch.long, device=preds.device) if want_argmax else None
+    return (*_fresh_mc_stat(preds, target, C, ignore_index, want_confmat, argmax), argmax)
 
 
 def mc_stat_labels(
     preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int], want_confmat: bool
 ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
     """Per-class tp/fp/fn (+confmat) from integer label predictions."""
-    lib = _lib()
-    preds = preds.contiguous().long().flatten()
-    target = target.contiguous().long().flatten()
-    N = preds.numel()
-    dev = preds.device
-    tp = torch.zeros(num_classes, dtype=torch.long, device=dev)
-    fp = torch.zeros(num_classes, dtype=torch.long, device=dev)
-    fn = torch.zeros(num_classes, dtype=torch.long, device=dev)
-    valid = torch.zeros(1, dtype=torch.long, device=dev)
-    confmat = torch.zeros(num_classes, num_classes, dtype=torch.long, device=dev) if want_confmat else None
-    rc = lib.ma_mc_stat_labels(
-        _stream(),
-        preds.data_ptr(),
-        target.data_ptr(),
-        N,
-        num_classes,
-        ignore_index if ignore_index is not None else 0,
-        1 if ignore_index is not None else 0,
-        tp.data_ptr(),
-        fp.data_ptr(),
-        fn.data_ptr(),
-        confmat.data_ptr() if confmat is not None else 0,
-        valid.data_ptr(),
-    )
-    _check(rc, "ma_mc_stat_labels")
-    return tp, fp, fn, valid, confmat
+    return _fresh_mc_stat(preds.long().flatten(), target, num_classes, ignore_index, want_confmat)
 
 
 def bincount(x: Tensor, minlength: int) -> Tensor:
@@ -1091,50 +1098,7 @@ def mc_stat_into(
     """
     lib = _lib()
     C = num_classes
-    s_tp = scratch[:C]
-    s_fp = scratch[C : 2 * C]
-    s_fn = scratch[2 * C : 3 * C]
-    s_valid_ptr = scratch.data_ptr() + 3 * C * 8
-    if preds.ndim == 2 and preds.is_floating_point():
-        preds = _to_supported(preds).contiguous()
-        target = target.contiguous().long()
-        B, C2 = preds.shape
-        rc = lib.ma_mc_stat_logits(
-            _stream(),
-            preds.data_ptr(),
-            _dtype_code(preds),
-            target.data_ptr(),
-            B,
-            C2,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            s_tp.data_ptr(),
-            s_fp.data_ptr(),
-            s_fn.data_ptr(),
-            0,
-            s_valid_ptr,
-            0,
-            0, 0, 0,
-        )
-        _check(rc, "ma_mc_stat_logits")
-    else:
-        p2 = preds.contiguous().long().flatten()
-        t2 = target.contiguous().long().flatten()
-        rc = lib.ma_mc_stat_labels(
-            _stream(),
-            p2.data_ptr(),
-            t2.data_ptr(),
-            p2.numel(),
-            C,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            s_tp.data_ptr(),
-            s_fp.data_ptr(),
-            s_fn.data_ptr(),
-            0,
-            s_valid_ptr,
-        )
-        _check(rc, "ma_mc_stat_labels")
+    _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch)
     rc = lib.ma_apply_stat_deltas(
         _stream(),
         scratch.data_ptr(),
@@ -1160,49 +1124,8 @@ def mc_confmat_into(
     the kernel also produces (never read, never zeroed: garbage accumulates
     harmlessly in int64).
     """
-    lib = _lib()
-    C = num_classes
     assert confmat_state.is_contiguous()
-    if preds.ndim == 2 and preds.is_floating_point():
-        preds = _to_supported(preds).contiguous()
-        target = target.contiguous().long()
-        B, C2 = preds.shape
-        rc = lib.ma_mc_stat_logits(
-            _stream(),
-            preds.data_ptr(),
-            _dtype_code(preds),
-            target.data_ptr(),
-            B,
-            C2,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            dummy[:C].data_ptr(),
-            dummy[C : 2 * C].data_ptr(),
-            dummy[2 * C : 3 * C].data_ptr(),
-            confmat_state.data_ptr(),
-            dummy[3 * C :].data_ptr(),
-            0,
-            0, 0, 0,
-        )
-        _check(rc, "ma_mc_stat_logits")
-    else:
-        p2 = preds.contiguous().long().flatten()
-        t2 = target.contiguous().long().flatten()
-        rc = lib.ma_mc_stat_labels(
-            _stream(),
-            p2.data_ptr(),
-            t2.data_ptr(),
-            p2.numel(),
-            C,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            dummy[:C].data_ptr(),
-            dummy[C : 2 * C].data_ptr(),
-            dummy[2 * C : 3 * C].data_ptr(),
-            confmat_state.data_ptr(),
-            dummy[3 * C :].data_ptr(),
-        )
-        _check(rc, "ma_mc_stat_labels")
+    _launch_mc_stat_scratch(preds, target, num_classes, ignore_index, dummy, confmat_state.data_ptr())
     _mark_kernel_mutated(confmat_state)
 
 
@@ -1218,47 +1141,7 @@ def mc_exact_into(
     """
     lib = _lib()
     C = num_classes
-    s_valid_ptr = scratch.data_ptr() + 3 * C * 8
-    if preds.ndim == 2 and preds.is_floating_point():
-        preds = _to_supported(preds).contiguous()
-        target = target.contiguous().long()
-        B, C2 = preds.shape
-        rc = lib.ma_mc_stat_logits(
-            _stream(),
-            preds.data_ptr(),
-            _dtype_code(preds),
-            target.data_ptr(),
-            B,
-            C2,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            scratch[:C].data_ptr(),
-            scratch[C : 2 * C].data_ptr(),
-            scratch[2 * C : 3 * C].data_ptr(),
-            0,
-            s_valid_ptr,
-            0,
-            0, 0, 0,
-        )
-        _check(rc, "ma_mc_stat_logits")
-    else:
-        p2 = preds.contiguous().long().flatten()
-        t2 = target.contiguous().long().flatten()
-        rc = lib.ma_mc_stat_labels(
-            _stream(),
-            p2.data_ptr(),
-            t2.data_ptr(),
-            p2.numel(),
-            C,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            scratch[:C].data_ptr(),
-            scratch[C : 2 * C].data_ptr(),
-            scratch[2 * C : 3 * C].data_ptr(),
-            0,
-            s_valid_ptr,
-        )
-        _check(rc, "ma_mc_stat_labels")
+    _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch)
     rc = lib.ma_exact_apply(
         _stream(),
         scratch.data_ptr(),
@@ -1367,37 +1250,11 @@ def mc_fused_collection_update(
     lib = _lib()
     C = num_classes
     scratch, tp, fp, tn, fn = stat
-    s_valid_ptr = scratch.data_ptr() + 3 * C * 8
-    if preds.ndim == 2 and preds.is_floating_point():
-        preds = _to_supported(preds).contiguous()
-        target = target.contiguous().long()
-        B = preds.shape[0]
-        rc = lib.ma_mc_stat_logits(
-            _stream(), preds.data_ptr(), _dtype_code(preds), target.data_ptr(),
-            B, C,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            scratch[:C].data_ptr(), scratch[C : 2 * C].data_ptr(), scratch[2 * C : 3 * C].data_ptr(),
-            confmat.data_ptr() if confmat is not None else 0,
-            s_valid_ptr, 0,
-            rowstats[0].data_ptr() if rowstats is not None else 0,
-            rowstats[1].data_ptr() if rowstats is not None else 0,
-            rowstats[2].data_ptr() if rowstats is not None else 0,
-        )
-        _check(rc, "ma_mc_stat_logits")
-    else:
-        p2 = preds.contiguous().long().flatten()
-        t2 = target.contiguous().long().flatten()
-        B = t2.numel()
-        rc = lib.ma_mc_stat_labels(
-            _stream(), p2.data_ptr(), t2.data_ptr(), B, C,
-            ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            scratch[:C].data_ptr(), scratch[C : 2 * C].data_ptr(), scratch[2 * C : 3 * C].data_ptr(),
-            confmat.data_ptr() if confmat is not None else 0,
-            s_valid_ptr,
-        )
-        _check(rc, "ma_mc_stat_labels")
+    B = _launch_mc_stat_scratch(
+        preds, target, C, ignore_index, scratch,
+        confmat.data_ptr() if confmat is not None else 0, rowstats,
+    )
+
     def _apply_pass() -> None:
         # fused epilogue: stat-delta apply (+ exact-match) in ONE launch; when
         # the lazy curve hist rides the same stream the caller defers this so
