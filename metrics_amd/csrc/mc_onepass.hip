@@ -8,11 +8,16 @@
 // registers (16 B per lane per vector, NV vectors per lane), so the row is
 // read from HBM once:
 //
-//  phase A  what k_mc_stat_logits does, through the same functions: both call
-//           softmax_fold / softmax_merge_wave, argmax_fold / argmax_merge_wave
-//           and count_row of row_fold.h (8-wide groups for bf16, 4-wide for
-//           fp32), so rowmax/rowinv and every count are bit-identical to the
-//           two-kernel path by construction.
+//  phase A  what k_mc_stat_logits does: both call softmax_fold /
+//           softmax_merge_wave and count_row of row_fold.h (8-wide groups for
+//           bf16, 4-wide for fp32), so rowmax/rowinv are bit-identical to the
+//           two-kernel path by construction. The argmax is taken by value
+//           first and index after (wave_max_f32, row_argmax_index,
+//           wave_min_u32), which the register-held row allows; the streaming
+//           kernel carries (value, index) through argmax_fold /
+//           argmax_merge_wave. Both implement one exact rule — largest
+//           non-NaN value, lowest index on a tie — so the counts agree by
+//           specification (tests/unittests/gpu/test_row_argmax_edges.py).
 //  phase B  CERTAINTY RULE: if this row itself holds an element outside
 //           [0,1], the batch-global answer is already known to be "softmax",
 //           and the row is binned from registers right away. A row with every
@@ -23,10 +28,11 @@
 // TWO LAUNCHES PER STEP. k_mc_onepass ends with ONE 16-byte record per block
 // (valid, binned, deferred + the block's "outside" bit, correct) instead of
 // atomics on single global words: 1024 blocks finishing together on three
-// words serialise. k_onepass_tail reads the records across the kernel
-// boundary; every one of its blocks sums all of them and so knows the
-// batch-global counts and the softmax decision on its own — no epoch flag, no
-// ticket, no wait. Its first ceil(C/256) blocks each apply a class slice of
+// words serialise, plus one flag byte (deferred a row / outside).
+// k_onepass_tail reads them across the kernel boundary; every one of its
+// blocks ORs all flag bytes and so knows whether rows wait and the softmax
+// decision on its own, the blocks with an epilogue slice also sum the records
+// for the batch-global counts — no epoch flag, no ticket, no wait. Its first ceil(C/256) blocks each apply a class slice of
 // the epilogue, block 0 also the scalars and the epoch bump, and when rows
 // were deferred all blocks grid-stride over the (class-chunk, 256-row) tiles
 // of the deferred pass (curve_hist_tile, shared with kernels.hip).
@@ -56,7 +62,7 @@
 typedef long long ll;
 typedef unsigned long long ull;
 
-// curve scratch layout (u64): [P: C][N1: C][N0: NCOPY x C][records: 2 x GRID_MAX]
+// curve scratch layout (u64): [P: C][N1: C][N0: NCOPY x C][records: 2 x GRID_MAX][flags: GRID_MAX / 8]
 // N0[c] takes ~150 increments per class and step at the bench shape; on one
 // address they serialise (measured: 10 us of the kernel). NCOPY copies, picked
 // by block index (consecutive blocks land on different XCDs), spread them; the
@@ -68,7 +74,12 @@ typedef unsigned long long ull;
 #define ONEPASS_NCOPY 8
 #define ONEPASS_GRID_MAX 1024  // records the scratch holds = cap of MA_ONEPASS_GRID
 #define ONEPASS_REC_OFF(C) ((2 + ONEPASS_NCOPY) * (C))
-#define ONEPASS_CS_WORDS(C) (ONEPASS_REC_OFF(C) + 2 * ONEPASS_GRID_MAX)
+// flags: one byte per k_mc_onepass block behind the records, bit 0 = the block
+// deferred a row, bit 1 = its "outside" bit: all a tail block without an
+// epilogue slice needs, 1 KB instead of the 16 KB of records. Overwritten every
+// step like the records; the tail reads exactly `grid` of them.
+#define ONEPASS_FLAG_OFF(C) (ONEPASS_REC_OFF(C) + 2 * ONEPASS_GRID_MAX)
+#define ONEPASS_CS_WORDS(C) (ONEPASS_FLAG_OFF(C) + ONEPASS_GRID_MAX / 8)
 #define ONEPASS_TAIL_GRID_DEFAULT 4096  // blocks of k_onepass_tail, see ma_mc_onepass_update
 
 template <typename T_, int NV>
@@ -78,7 +89,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     ull* __restrict__ confmat, float* __restrict__ rowmax, float* __restrict__ rowinv,
     const float* __restrict__ thresholds, int T, int uniform, float t0, float inv_step,
     ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cs /* [P|N1|N0 copies] */,
-    uint4* __restrict__ records /* gridDim.x */) {
+    uint4* __restrict__ records /* gridDim.x */, unsigned char* __restrict__ flags /* gridDim.x */) {
     constexpr int EPV = 16 / sizeof(T_);  // elements per 16-byte vector
     extern __shared__ float sthr[];
     __shared__ unsigned int block_valid, blk_outside, blk_binned, blk_deferred, blk_correct;
@@ -119,8 +130,11 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         const ll t = target[row];
 
         // ---- phase A: the folds of k_mc_stat_logits (row_fold.h) ----
+        // The row stays in registers, so the argmax index need not ride
+        // through the fold: the fold keeps the lane's largest value (not the
+        // softmax m, which starts at -3.4e38 rather than -inf), the index is
+        // looked up once the row's maximum is known.
         float best = -INFINITY;
-        int best_idx = 0x7fffffff;
         float sm_m = -3.4e38f, sm_s = 0.0f;  // online softmax (max, sumexp)
         unsigned int row_out = 0;
 #pragma unroll
@@ -129,8 +143,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             if (v < nvec) {
                 float f[EPV];
                 unpack16<T_>(r[k], f);
-                softmax_fold(f, sm_m, sm_s, row_out);
-                argmax_fold(f, v * EPV, best, best_idx);
+                best = fmaxf(best, softmax_fold(f, sm_m, sm_s, row_out));
             }
         }
         // an ignored row takes no part in the softmax decision (the reference
@@ -139,14 +152,19 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         if (ignored) row_out = 0u;
         outside |= row_out;
         softmax_merge_wave(sm_m, sm_s);
-        argmax_merge_wave(best, best_idx);
-        // lane 0 holds the row's (max, sumexp); every lane needs them for phase B
-        const float rmax = __shfl(sm_m, 0);
-        const float rinv = __shfl(1.0f / sm_s, 0);
+        const float rowbest = wave_max_f32(best);
+        const unsigned int best_idx =
+            wave_min_u32(row_argmax_index<T_, NV>(r, lane, nvec, rowbest));  // 0x7fffffff: all NaN
+        // lane 0 holds the row's (max, sumexp); every lane needs them for phase B.
+        // All 64 lanes are active here, so lane 0 is the first active lane:
+        // the values come over as scalars, with no LDS round trip.
+        const float rmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sm_m)));
+        const float rsum = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sm_s)));
+        const float rinv = 1.0f / rsum;
         const bool certain = __ballot(row_out != 0u) != 0ULL;  // this row alone proves "softmax"
         const bool bin_now = certain && !ignored;
         if (lane == 0) {
-            const ll p = best_idx;
+            const ll p = (ll)best_idx;
             if (count_row(t, p, C, ignored, tp, fp, fn, confmat)) {
                 my_valid++;
                 if (p == t) my_correct++;
@@ -184,8 +202,21 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             // the 1e-3 margin — such an element is certainly in b0 and costs
             // a subtract and a compare. Everything else, NaN included (the
             // compare is false), goes through expf and bucket_of unchanged.
-            const float dcut = logf(hi0 * __shfl(sm_s, 0)) - 1e-3f;
-            ull todo = 0;  // bit k*EPV+i: element i of vector k needs the full path
+            // The filter only has to be SAFE (an element it lets through is
+            // binned exactly all the same), so the subtract is hoisted out of
+            // the element loop: x < xcut with xcut = fl(rmax + dcut) lowered
+            // by 2^-22 |rmax|. fl() is off by at most 2^-24 (|rmax| + |dcut|):
+            // the |rmax| share is covered by the lowering (four times as
+            // large, its own rounding included), the |dcut| share (|dcut| <
+            // 100: below 1e-5) by the 1e-3 margin. rmax = +inf or a NaN sum
+            // make xcut NaN: every compare false, every element takes the
+            // full path.
+            const float dcut = logf(hi0 * rsum) - 1e-3f;
+            const float xcut = (rmax + dcut) - fabsf(rmax) * 2.4e-7f;
+            // bit k*EPV+i: element i of vector k needs the full path; 32 bits
+            // hold it for all but bf16 NV=8
+            typedef typename std::conditional<(EPV * NV <= 32), unsigned int, ull>::type todo_t;
+            todo_t todo = 0;
 #pragma unroll
             for (int k = 0; k < NV; k++) {
                 if (lane + k * WAVE < nvec) {
@@ -193,15 +224,17 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
                     unpack16<T_>(r[k], f);
 #pragma unroll
                     for (int i = 0; i < EPV; i++)
-                        todo |= (f[i] - rmax < dcut) ? 0ULL : (1ULL << (k * EPV + i));
+                        todo |= (f[i] < xcut) ? (todo_t)0 : ((todo_t)1 << (k * EPV + i));
                 }
             }
             // compacted: every lane pops one pending element per round, so a
             // row costs max-over-lanes(popcount) rounds, not EPV*NV
-            while (__ballot(todo != 0ULL) != 0ULL) {
-                if (todo != 0ULL) {
-                    const int e = __ffsll(todo) - 1;
-                    todo &= todo - 1ULL;
+            while (__ballot(todo != 0) != 0ULL) {
+                if (todo != 0) {
+                    int e;
+                    if constexpr (sizeof(todo_t) == 4) e = __ffs((int)todo) - 1;
+                    else e = __ffsll((ull)todo) - 1;
+                    todo &= todo - 1;
                     const int wi = is_bf16_v<T_> ? (e >> 1) : e;  // 32-bit word of the row slice
                     unsigned int w = r[0].x;
 #pragma unroll
@@ -233,12 +266,16 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         // one 16-byte store; a block holds < 2^31 rows, so bit 31 is free
         records[blockIdx.x] = make_uint4(block_valid, blk_binned,
                                          blk_deferred | (blk_outside << 31), blk_correct);
+        flags[blockIdx.x] = (unsigned char)((blk_deferred ? 1u : 0u) | (blk_outside ? 2u : 0u));
     }
 }
 
 // Tail of the one-pass step, the second and last launch. Every block:
-//  (a) sums the `grid` per-block records of k_mc_onepass (<= 16 KB, L2) and so
-//      holds valid / binned / deferred / outside / correct for the batch;
+//  (a) ORs the `grid` per-block flag bytes of k_mc_onepass (<= 1 KB, L2) and
+//      so knows whether any row was deferred and the softmax decision. Only
+//      the first ceil(C/256) blocks, which own an epilogue slice, also sum the
+//      16-byte records (<= 16 KB) for valid / binned / correct: with 4096
+//      blocks that is 4 MB of L2 reads per step in place of 64 MB;
 //  (b) applies the epilogue for class blockIdx.x*256 + threadIdx.x, if there
 //      is one: k_apply_stat_exact's stat deltas plus the complement fill of
 //      bucket b0. Each slot of both scratches is read and zeroed by the same
@@ -252,7 +289,8 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
 // or grid-wide wait.
 template <typename T_>
 __global__ void __launch_bounds__(256) k_onepass_tail(
-    const uint4* __restrict__ records, int grid /* blocks k_mc_onepass ran with */,
+    const uint4* __restrict__ records, const unsigned char* __restrict__ flags,
+    int grid /* blocks k_mc_onepass ran with */,
     ull* __restrict__ scratch /* 3*C + 1 */, ll C, ll B, ll* __restrict__ tp, ll* __restrict__ fp,
     ll* __restrict__ tn, ll* __restrict__ fn, ll* __restrict__ correct /* nullable */,
     ll* __restrict__ total, unsigned int* __restrict__ E, ull* __restrict__ cs /* [P|N1|N0 copies] */,
@@ -264,37 +302,43 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     __shared__ unsigned int wsum[256 / WAVE][5];
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x / WAVE;
+    // block-uniform: this block owns classes blockIdx.x*256 ... (block 0 always does)
+    const bool has_slice = (ll)blockIdx.x * blockDim.x < C;
 
-    // ---- (a) the batch-global counts ----
-    unsigned int r_valid = 0, r_binned = 0, r_deferred = 0, r_correct = 0, r_outside = 0;
-    for (int i = threadIdx.x; i < grid; i += blockDim.x) {
-        const uint4 r = records[i];
-        r_valid += r.x;
-        r_binned += r.y;
-        r_deferred += r.z & 0x7fffffffu;
-        r_outside |= r.z >> 31;
-        r_correct += r.w;
+    // ---- (a) the batch-global flags; the counts where the epilogue needs them ----
+    unsigned int fl = 0;
+    for (int i = threadIdx.x; i < grid; i += blockDim.x) fl |= flags[i];
+    unsigned int r_valid = 0, r_binned = 0, r_correct = 0;
+    if (has_slice) {
+        for (int i = threadIdx.x; i < grid; i += blockDim.x) {
+            const uint4 r = records[i];
+            r_valid += r.x;
+            r_binned += r.y;
+            r_correct += r.w;
+        }
     }
     for (int b = threadIdx.x; b < T; b += blockDim.x) sthr_t[b] = thresholds[b];
-    for (int off = WAVE / 2; off > 0; off >>= 1) {
-        r_valid += __shfl_down(r_valid, off);
-        r_binned += __shfl_down(r_binned, off);
-        r_deferred += __shfl_down(r_deferred, off);
-        r_correct += __shfl_down(r_correct, off);
-        r_outside |= __shfl_down(r_outside, off);
+    if (has_slice) {
+        for (int off = WAVE / 2; off > 0; off >>= 1) {
+            r_valid += __shfl_down(r_valid, off);
+            r_binned += __shfl_down(r_binned, off);
+            r_correct += __shfl_down(r_correct, off);
+        }
     }
+    const unsigned int wave_fl = (__ballot(fl & 1u) != 0ULL ? 1u : 0u) | (__ballot(fl & 2u) != 0ULL ? 2u : 0u);
     if (lane == 0) {
-        wsum[wave][0] = r_valid; wsum[wave][1] = r_binned; wsum[wave][2] = r_deferred;
-        wsum[wave][3] = r_correct; wsum[wave][4] = r_outside;
+        wsum[wave][0] = r_valid; wsum[wave][1] = r_binned; wsum[wave][2] = r_correct;
+        wsum[wave][3] = wave_fl;
     }
     __syncthreads();
     ll valid = 0, binned = 0;
-    unsigned int deferred = 0, ncorrect = 0, outside = 0;
+    unsigned int ncorrect = 0, all_fl = 0;
 #pragma unroll
     for (int w = 0; w < 256 / WAVE; w++) {
-        valid += wsum[w][0]; binned += wsum[w][1]; deferred += wsum[w][2];
-        ncorrect += wsum[w][3]; outside |= wsum[w][4];
+        valid += wsum[w][0]; binned += wsum[w][1]; ncorrect += wsum[w][2]; all_fl |= wsum[w][3];
     }
+    const bool deferred = (all_fl & 1u) != 0;  // some row waits for this kernel
+    const unsigned int outside = all_fl >> 1;
 
     // ---- (b) epilogue for one class ----
     const ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
@@ -326,7 +370,7 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     }
 
     // ---- (c) the deferred rows ----
-    if (deferred == 0) return;
+    if (!deferred) return;
     const int norm = outside ? 1 : 0;  // softmax iff any element of the batch lay outside [0,1]
     // Tile t -> (class chunk, row tile). Blocks go round-robin over the 8 XCDs
     // (each with its own L2) and adjacent class chunks read slices of the SAME
@@ -379,19 +423,6 @@ int ma_mc_onepass_nv(int dtype /*0=f32 1=bf16*/, ll C, int T) {
 // u64 words of the curve scratch for C classes (records region included)
 int ma_mc_onepass_scratch_words(ll C) { return (int)ONEPASS_CS_WORDS(C); }
 
-#define ONEPASS_LAUNCH(DT_, NV_)                                                                 \
-    k_mc_onepass<DT_, NV_><<<grid, 256, shmem, s>>>(                                             \
-        (const uint4*)preds, (const ll*)target, B, C, ignore_index, has_ignore, sc, sc + C,      \
-        sc + 2 * C, (ull*)confmat, (float*)rowmax, (float*)rowinv, (const float*)thresholds, T,  \
-        uniform, t0, inv_step, (ull*)hist, (ull*)cscratch, records)
-#define ONEPASS_LAUNCH_NV(DT_)                                                                   \
-    do {                                                                                         \
-        if (nv == 1) ONEPASS_LAUNCH(DT_, 1);                                                     \
-        else if (nv == 2) ONEPASS_LAUNCH(DT_, 2);                                                \
-        else if (nv == 4) ONEPASS_LAUNCH(DT_, 4);                                                \
-        else ONEPASS_LAUNCH(DT_, 8);                                                             \
-    } while (0)
-
 // blocks of k_mc_onepass for B rows: one row per wave and pass, 4 waves per
 // block. Measured at B=8192 C=1000 (sweep knob MA_ONEPASS_GRID): 2048 blocks —
 // every row resident at once — run the load, fold and binning phases chip-wide
@@ -411,32 +442,65 @@ static int onepass_grid(ll B) {
     return (int)g;
 }
 
+// cap of the tail grid, sweep knob MA_ONEPASS_TAIL_GRID (see onepass_step)
+static int onepass_tail_cap() {
+    static int tcap = 0;
+    if (tcap == 0) {
+        const char* e = getenv("MA_ONEPASS_TAIL_GRID");
+        tcap = e ? atoi(e) : ONEPASS_TAIL_GRID_DEFAULT;
+        if (tcap < 8) tcap = 8;
+        if (tcap > 65536) tcap = 65536;
+    }
+    return tcap;
+}
+
+}  // extern "C"
+
+// Everything of a step that stays the same from one step to the next: shape,
+// thresholds and the addresses of the states and scratches. The caller owns
+// the memory behind the addresses and keeps it alive as long as the plan.
+struct OnepassPlan {
+    int dtype, nv, T, uniform, has_ignore;
+    ll C, ignore_index;
+    float t0, inv_step;
+    ull *scratch, *confmat, *hist, *cscratch;
+    ll *tp, *fp, *tn, *fn, *correct, *total;
+    float *rowmax, *rowinv;
+    unsigned int* epoch_buf;
+    const float* thresholds;
+};
+
+template <typename T_, int NV>
+static void onepass_launch_main(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
+                                const ll* target, ll B, uint4* records, unsigned char* flags) {
+    ull* sc = p.scratch;
+    k_mc_onepass<T_, NV><<<grid, 256, (size_t)p.T * sizeof(float), s>>>(
+        (const uint4*)preds, target, B, p.C, p.ignore_index, p.has_ignore, sc, sc + p.C,
+        sc + 2 * p.C, p.confmat, p.rowmax, p.rowinv, p.thresholds, p.T, p.uniform, p.t0,
+        p.inv_step, p.hist, p.cscratch, records, flags);
+}
+template <typename T_>
+static void onepass_launch_nv(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
+                              const ll* target, ll B, uint4* records, unsigned char* flags) {
+    if (p.nv == 1) onepass_launch_main<T_, 1>(p, s, grid, preds, target, B, records, flags);
+    else if (p.nv == 2) onepass_launch_main<T_, 2>(p, s, grid, preds, target, B, records, flags);
+    else if (p.nv == 4) onepass_launch_main<T_, 4>(p, s, grid, preds, target, B, records, flags);
+    else onepass_launch_main<T_, 8>(p, s, grid, preds, target, B, records, flags);
+}
+
 // The whole fused-collection step on one stream in two launches: one-pass
 // kernel, tail kernel (B == 0: the tail alone, which then is the epilogue).
-// scratch = stat scratch [tp|fp|fn|valid] (3*C+1 u64; the valid slot is not
-// used here), cscratch = curve scratch [P|N1|N0 copies|records]
-// (ma_mc_onepass_scratch_words(C) u64); the counters of both are zero on entry
-// and zero again after the tail, the records need no zeroing.
-// correct/total may be 0 (no exact-match leader).
-int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t target, ll B,
-                         ll C, ll ignore_index, int has_ignore, uintptr_t scratch,
-                         uintptr_t confmat, uintptr_t tp, uintptr_t fp, uintptr_t tn, uintptr_t fn,
-                         uintptr_t correct, uintptr_t total, uintptr_t rowmax, uintptr_t rowinv,
-                         uintptr_t epoch_buf, uintptr_t thresholds, int T, int uniform, float t0,
-                         float inv_step, uintptr_t hist, uintptr_t cscratch) {
-    hipStream_t s = (hipStream_t)stream;
-    const int nv = ma_mc_onepass_nv(dtype, C, T);
-    if (nv == 0 || (preds & 15) || (cscratch & 15) || !scratch || !cscratch || !hist || !rowmax ||
-        !rowinv || !epoch_buf || !thresholds)
-        return -103;
+static int onepass_step(const OnepassPlan& p, hipStream_t s, uintptr_t preds, uintptr_t target,
+                        ll B) {
+    if (preds & 15) return -103;
     if (B < 0 || B >= (1LL << 31)) return -101;  // u32 counts in the records
-    const size_t shmem = (size_t)T * sizeof(float);
-    uint4* records = (uint4*)((ull*)cscratch + ONEPASS_REC_OFF(C));
+    const ll C = p.C;
+    uint4* records = (uint4*)(p.cscratch + ONEPASS_REC_OFF(C));
+    unsigned char* flags = (unsigned char*)(p.cscratch + ONEPASS_FLAG_OFF(C));
     const int grid = B > 0 ? onepass_grid(B) : 0;
     if (B > 0) {
-        ull* sc = (ull*)scratch;
-        if (dtype == 0) ONEPASS_LAUNCH_NV(float);
-        else ONEPASS_LAUNCH_NV(unsigned short);
+        if (p.dtype == 0) onepass_launch_nv<float>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
+        else onepass_launch_nv<unsigned short>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -450,13 +514,7 @@ int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
     // blocks as fit lets the dispatcher balance them (torch.rand inputs 361 us
     // at 2048, 347 at 4000, the three-launch step 347-348) for 2.5 us of the
     // logits loop.
-    static int tcap = 0;
-    if (tcap == 0) {
-        const char* e = getenv("MA_ONEPASS_TAIL_GRID");
-        tcap = e ? atoi(e) : ONEPASS_TAIL_GRID_DEFAULT;
-        if (tcap < 8) tcap = 8;
-        if (tcap > 65536) tcap = 65536;
-    }
+    const int tcap = onepass_tail_cap();
     const ll row_chunks = (B + 255) / 256;
     int c_chunk = 4;
     while (c_chunk > 1 && ((C + c_chunk - 1) / c_chunk) * row_chunks < 4096) c_chunk /= 2;
@@ -465,12 +523,86 @@ int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t
     const ll eblocks = (C + 255) / 256;
     if (tg < eblocks) tg = eblocks;
     const int tgrid = (int)((tg + 7) / 8 * 8);  // multiple of 8: block % 8 is the XCD
-    LAUNCH_BY_DTYPE(dtype, k_onepass_tail, tgrid, 256, shmem, s, records, grid, (ull*)scratch, C, B,
-                    (ll*)tp, (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct, (ll*)total,
-                    (unsigned int*)epoch_buf, (ull*)cscratch, (const float*)thresholds, T,
-                    (ull*)hist, (const DT*)preds, (const ll*)target, ignore_index, has_ignore,
-                    uniform, t0, inv_step, c_chunk, (const float*)rowmax, (const float*)rowinv);
+    LAUNCH_BY_DTYPE(p.dtype, k_onepass_tail, tgrid, 256, (size_t)p.T * sizeof(float), s, records,
+                    flags, grid, p.scratch, C, B, p.tp, p.fp, p.tn, p.fn, p.correct, p.total, p.epoch_buf,
+                    p.cscratch, p.thresholds, p.T, p.hist, (const DT*)preds, (const ll*)target,
+                    p.ignore_index, p.has_ignore, p.uniform, p.t0, p.inv_step, c_chunk,
+                    (const float*)p.rowmax, (const float*)p.rowinv);
     return (int)hipGetLastError();
+}
+
+// Fill a plan; -103 for a shape the kernel does not cover or a missing /
+// misaligned buffer. scratch = stat scratch [tp|fp|fn|valid] (3*C+1 u64; the
+// valid slot is not used here), cscratch = curve scratch [P|N1|N0
+// copies|records] (ma_mc_onepass_scratch_words(C) u64); the counters of both
+// are zero before the first step and zero again after every tail, the records
+// need no zeroing. correct/total may be 0 (no exact-match leader).
+static int onepass_plan_fill(OnepassPlan& p, int dtype, ll C, ll ignore_index, int has_ignore,
+                             uintptr_t scratch, uintptr_t confmat, uintptr_t tp, uintptr_t fp,
+                             uintptr_t tn, uintptr_t fn, uintptr_t correct, uintptr_t total,
+                             uintptr_t rowmax, uintptr_t rowinv, uintptr_t epoch_buf,
+                             uintptr_t thresholds, int T, int uniform, float t0, float inv_step,
+                             uintptr_t hist, uintptr_t cscratch) {
+    const int nv = ma_mc_onepass_nv(dtype, C, T);
+    if (nv == 0 || (cscratch & 15) || !scratch || !cscratch || !hist || !rowmax || !rowinv ||
+        !epoch_buf || !thresholds)
+        return -103;
+    p.dtype = dtype; p.nv = nv; p.T = T; p.uniform = uniform; p.has_ignore = has_ignore;
+    p.C = C; p.ignore_index = ignore_index; p.t0 = t0; p.inv_step = inv_step;
+    p.scratch = (ull*)scratch; p.confmat = (ull*)confmat; p.hist = (ull*)hist;
+    p.cscratch = (ull*)cscratch;
+    p.tp = (ll*)tp; p.fp = (ll*)fp; p.tn = (ll*)tn; p.fn = (ll*)fn;
+    p.correct = (ll*)correct; p.total = (ll*)total;
+    p.rowmax = (float*)rowmax; p.rowinv = (float*)rowinv;
+    p.epoch_buf = (unsigned int*)epoch_buf; p.thresholds = (const float*)thresholds;
+    return 0;
+}
+
+extern "C" {
+
+// Step plan: create once per set of states, step every update (stream, preds,
+// target and B are all that changes), destroy when the states are replaced.
+// *handle is written only on success.
+int ma_onepass_plan_create(int dtype, ll C, ll ignore_index, int has_ignore, uintptr_t scratch,
+                           uintptr_t confmat, uintptr_t tp, uintptr_t fp, uintptr_t tn,
+                           uintptr_t fn, uintptr_t correct, uintptr_t total, uintptr_t rowmax,
+                           uintptr_t rowinv, uintptr_t epoch_buf, uintptr_t thresholds, int T,
+                           int uniform, float t0, float inv_step, uintptr_t hist,
+                           uintptr_t cscratch, unsigned long long* handle) {
+    OnepassPlan* p = new OnepassPlan;
+    const int rc = onepass_plan_fill(*p, dtype, C, ignore_index, has_ignore, scratch, confmat, tp,
+                                     fp, tn, fn, correct, total, rowmax, rowinv, epoch_buf,
+                                     thresholds, T, uniform, t0, inv_step, hist, cscratch);
+    if (rc != 0) { delete p; return rc; }
+    *handle = (unsigned long long)(uintptr_t)p;
+    return 0;
+}
+
+int ma_onepass_plan_step(uintptr_t handle, uintptr_t stream, uintptr_t preds, uintptr_t target,
+                         ll B) {
+    if (!handle) return -103;
+    return onepass_step(*(const OnepassPlan*)handle, (hipStream_t)stream, preds, target, B);
+}
+
+void ma_onepass_plan_destroy(uintptr_t handle) { delete (OnepassPlan*)handle; }
+
+// One step without a kept plan: the same fill and the same step as
+// create / step / destroy, so every caller goes through the same launches and
+// gets the same codes.
+int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t target, ll B,
+                         ll C, ll ignore_index, int has_ignore, uintptr_t scratch,
+                         uintptr_t confmat, uintptr_t tp, uintptr_t fp, uintptr_t tn, uintptr_t fn,
+                         uintptr_t correct, uintptr_t total, uintptr_t rowmax, uintptr_t rowinv,
+                         uintptr_t epoch_buf, uintptr_t thresholds, int T, int uniform, float t0,
+                         float inv_step, uintptr_t hist, uintptr_t cscratch) {
+    unsigned long long h = 0;
+    const int rc = ma_onepass_plan_create(dtype, C, ignore_index, has_ignore, scratch, confmat, tp,
+                                          fp, tn, fn, correct, total, rowmax, rowinv, epoch_buf,
+                                          thresholds, T, uniform, t0, inv_step, hist, cscratch, &h);
+    if (rc != 0) return rc;
+    const int rs = ma_onepass_plan_step((uintptr_t)h, stream, preds, target, B);
+    ma_onepass_plan_destroy((uintptr_t)h);
+    return rs;
 }
 
 }  // extern "C"

@@ -2,8 +2,9 @@
 // mc_onepass.hip): element loads keyed on the dtype, the online-softmax and
 // argmax folds with their 64-lane merges, the per-row counting, the epoch
 // publish and the stat-delta epilogue. The one-pass step must equal the
-// two-kernel step bit for bit; both call these functions, so "same fold" holds
-// by construction. Each kernel only picks its group width K per shape — K
+// two-kernel step bit for bit; both call the softmax functions, so "same fold"
+// holds by construction, and the two argmax forms (carried index / value first,
+// for a row held in registers) follow one exact rule. Each kernel only picks its group width K per shape — K
 // changes the rounding of rowinv, so a kernel's choice is part of its contract.
 #pragma once
 
@@ -71,33 +72,123 @@ __device__ __forceinline__ void unpack16(const uint4& u, float (&f)[16 / sizeof(
     }
 }
 
-// ---- online softmax: (m, s) = (running max, sum of exp(x - m)) ----
-// Fold a group of K elements: group max first, then the group's sum, then the
-// two-way merge into (m, s). row_out collects the "outside [0,1]" bit.
-template <int K>
-__device__ __forceinline__ void softmax_fold(const float (&f)[K], float& m, float& s,
-                                             unsigned int& row_out) {
-    float mk = f[0];
-#pragma unroll
-    for (int i = 1; i < K; i++) mk = fmaxf(mk, f[i]);
-    float sk = 0.0f;
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        row_out |= (f[i] < 0.0f || f[i] > 1.0f) ? 1u : 0u;
-        sk += __expf(f[i] - mk);
+// ---- 64-lane exchanges without LDS ----
+// MA_ROWFOLD_XLANE=0 builds every merge below on __shfl_down (ds_bpermute, an
+// LDS round trip per step) instead: the A/B lever for profiles/README.md.
+#ifndef MA_ROWFOLD_XLANE
+#define MA_ROWFOLD_XLANE 1
+#endif
+
+// value of lane l + OFF for the lanes a __shfl_down tree towards lane 0 reads
+// (l < OFF); the other lanes get an unspecified value. All 64 lanes must be
+// active. OFF <= 8 is a DPP row shift (row_shl: lane l reads l + OFF of its
+// 16-lane row), 16 and 32 are the half-row / half-wave swaps: with both
+// operands the same register, the second result holds lane l + OFF for l in
+// the lower half of each pair.
+template <int OFF>
+__device__ __forceinline__ unsigned int lane_down_u32(unsigned int x) {
+#if MA_ROWFOLD_XLANE
+    if constexpr (OFF == 32) {
+        return __builtin_amdgcn_permlane32_swap(x, x, false, false)[1];
+    } else if constexpr (OFF == 16) {
+        return __builtin_amdgcn_permlane16_swap(x, x, false, false)[1];
+    } else {
+        static_assert(OFF >= 1 && OFF <= 8, "row shift");
+        return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)x, 0x100 + OFF, 0xf, 0xf, true);
     }
-    if (mk > m) { s = s * __expf(m - mk) + sk; m = mk; }
-    else { s += sk * __expf(mk - m); }
+#else
+    return (unsigned int)__shfl_down((int)x, OFF);
+#endif
+}
+template <int OFF>
+__device__ __forceinline__ float lane_down(float x) {
+    return __uint_as_float(lane_down_u32<OFF>(__float_as_uint(x)));
 }
 
-// 64-lane merge; the row's (m, s) lands in lane 0
+// max of a float / min of an unsigned over the 64 lanes, returned to every
+// lane (wave-uniform); all 64 lanes must be active. Both are idempotent, so the butterfly may fold a lane's
+// own value in twice: quad swaps, row rotates by 4 and 8 (every lane of a
+// 16-lane row then holds the row's result), row_bcast15 into rows 1 and 3,
+// row_bcast31 into rows 2 and 3; lane 63 holds the wave's. `old` = the value
+// itself keeps the rows a broadcast does not write unchanged. NaN never wins
+// the max (fmaxf drops it).
+#define MA_DPP_STEP(v, ctrl, rows) __builtin_amdgcn_update_dpp((v), (v), (ctrl), (rows), 0xf, false)
+__device__ __forceinline__ float wave_max_f32(float x) {
+#if MA_ROWFOLD_XLANE
+    auto step = [](float v, int o) { return fmaxf(v, __int_as_float(o)); };
+    x = step(x, MA_DPP_STEP(__float_as_int(x), 0xb1, 0xf));   // quad_perm [1,0,3,2]
+    x = step(x, MA_DPP_STEP(__float_as_int(x), 0x4e, 0xf));   // quad_perm [2,3,0,1]
+    x = step(x, MA_DPP_STEP(__float_as_int(x), 0x124, 0xf));  // row_ror 4
+    x = step(x, MA_DPP_STEP(__float_as_int(x), 0x128, 0xf));  // row_ror 8
+    x = step(x, MA_DPP_STEP(__float_as_int(x), 0x142, 0xa));  // row_bcast15
+    x = step(x, MA_DPP_STEP(__float_as_int(x), 0x143, 0xc));  // row_bcast31
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+#else
+    for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_down(x, off));
+    return __shfl(x, 0);
+#endif
+}
+__device__ __forceinline__ unsigned int wave_min_u32(unsigned int x) {
+#if MA_ROWFOLD_XLANE
+    auto step = [](unsigned int v, int o) { return min(v, (unsigned int)o); };
+    x = step(x, MA_DPP_STEP((int)x, 0xb1, 0xf));
+    x = step(x, MA_DPP_STEP((int)x, 0x4e, 0xf));
+    x = step(x, MA_DPP_STEP((int)x, 0x124, 0xf));
+    x = step(x, MA_DPP_STEP((int)x, 0x128, 0xf));
+    x = step(x, MA_DPP_STEP((int)x, 0x142, 0xa));
+    x = step(x, MA_DPP_STEP((int)x, 0x143, 0xc));
+    return (unsigned int)__builtin_amdgcn_readlane((int)x, 63);
+#else
+    for (int off = 32; off > 0; off >>= 1) x = min(x, (unsigned int)__shfl_down((int)x, off));
+    return (unsigned int)__shfl((int)x, 0);
+#endif
+}
+#undef MA_DPP_STEP
+
+// ---- online softmax: (m, s) = (running max, sum of exp(x - m)) ----
+// Fold a group of K elements: group max first, then the group's sum, then the
+// two-way merge into (m, s). row_out collects the "outside [0,1]" bit, taken
+// from the group's extremes: some f[i] < 0 or > 1 <=> min < 0 or max > 1.
+// fminf/fmaxf drop NaN and both compares are false for NaN, as the per-element
+// test was (an all-NaN group leaves mn = mk = NaN: no bit). Returns the group
+// maximum (NaN only for an all-NaN group).
+template <int K>
+__device__ __forceinline__ float softmax_fold(const float (&f)[K], float& m, float& s,
+                                              unsigned int& row_out) {
+    float mk = f[0], mn = f[0];
+#pragma unroll
+    for (int i = 1; i < K; i++) { mk = fmaxf(mk, f[i]); mn = fminf(mn, f[i]); }
+    row_out |= (mn < 0.0f || mk > 1.0f) ? 1u : 0u;
+    float sk = 0.0f;
+#pragma unroll
+    for (int i = 0; i < K; i++) sk += __expf(f[i] - mk);
+    if (mk > m) { s = s * __expf(m - mk) + sk; m = mk; }
+    else { s += sk * __expf(mk - m); }
+    return mk;
+}
+
+// One step of the 64-lane merge, branch-free. Either order of the two-way
+// merge scales by exp(smaller max - larger max); m is never NaN (the fold
+// never stores one), so that is one __expf for both. fmaf spelled out: the
+// two-branch form this replaces contracted to the same fused multiply-adds,
+// and rowinv keeps its bits. m takes om only when om > m, so a -0.0 / +0.0
+// pair keeps the sign it kept before.
+__device__ __forceinline__ void softmax_merge_step(float& m, float& s, float om, float os) {
+    const float e = __expf(fminf(m, om) - fmaxf(m, om));
+    const bool up = om > m;
+    s = up ? fmaf(s, e, os) : fmaf(os, e, s);
+    m = up ? om : m;
+}
+
+// 64-lane merge, lane l with lane l + off for off = 32 ... 1; the row's (m, s)
+// lands in lane 0
 __device__ __forceinline__ void softmax_merge_wave(float& m, float& s) {
-    for (int off = 32; off > 0; off >>= 1) {
-        float om = __shfl_down(m, off);
-        float os = __shfl_down(s, off);
-        if (om > m) { s = s * __expf(m - om) + os; m = om; }
-        else { s += os * __expf(om - m); }
-    }
+    softmax_merge_step(m, s, lane_down<32>(m), lane_down<32>(s));
+    softmax_merge_step(m, s, lane_down<16>(m), lane_down<16>(s));
+    softmax_merge_step(m, s, lane_down<8>(m), lane_down<8>(s));
+    softmax_merge_step(m, s, lane_down<4>(m), lane_down<4>(s));
+    softmax_merge_step(m, s, lane_down<2>(m), lane_down<2>(s));
+    softmax_merge_step(m, s, lane_down<1>(m), lane_down<1>(s));
 }
 
 // ---- argmax, lowest index on a tie (torch.argmax); c = index of f[0] ----
@@ -117,6 +208,34 @@ __device__ __forceinline__ void argmax_merge_wave(float& best, Idx& best_idx) {
         Idx oi = __shfl_down(best_idx, off);
         if (ov > best || (ov == best && oi < best_idx)) { best = ov; best_idx = oi; }
     }
+}
+
+// ---- argmax of a row held in registers: value first, index after ----
+// The same rule as argmax_fold / argmax_merge_wave (largest non-NaN value,
+// lowest index on a tie, 0x7fffffff when every element is NaN), for a kernel
+// that still has the row when the maximum is known. During the fold a lane
+// keeps only best = fmaxf(best, group max), starting at -INFINITY (an all-NaN
+// group leaves it alone); rowbest = wave_max_f32(best); then
+// row_argmax_index(): the lowest index this lane holds with f == rowbest
+// (+0.0 and -0.0 tie, as they do under > and ==; a row of -inf matches at its
+// first -inf; NaN matches nothing), and wave_min_u32 over the lanes.
+// r[k] is vector lane + 64*k of the row; vectors at or past nvec hold no data.
+template <typename T, int NV>
+__device__ __forceinline__ unsigned int row_argmax_index(const uint4 (&r)[NV], int lane, int nvec,
+                                                         float rowbest) {
+    constexpr int EPV = 16 / sizeof(T);
+    unsigned int idx = 0x7fffffffu;
+#pragma unroll
+    for (int k = NV - 1; k >= 0; k--) {  // descending: the lowest match is written last
+        const int v = lane + k * 64;
+        if (v < nvec) {
+            float f[EPV];
+            unpack16<T>(r[k], f);
+#pragma unroll
+            for (int i = EPV - 1; i >= 0; i--) idx = (f[i] == rowbest) ? (unsigned int)(v * EPV + i) : idx;
+        }
+    }
+    return idx;
 }
 
 // ---- one row's counts (called by the lane that holds target and argmax) ----

@@ -10,6 +10,7 @@ updates must never silently fall back to stock torch kernels on MI355X.
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 from typing import Optional, Tuple
 
@@ -62,6 +63,8 @@ _SIGNATURES = {
     "ma_mc_onepass_nv": [_I, _LL, _I],
     "ma_mc_onepass_scratch_words": [_LL],
     "ma_mc_onepass_update": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64],
+    "ma_onepass_plan_create": [_I, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64, ctypes.POINTER(ctypes.c_ulonglong)],
+    "ma_onepass_plan_step": [_U64, _U64, _U64, _U64, _LL],
     "ma_apply_stat_exact": [_U64, _U64, _LL, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
     "ma_curve_auc_from_confmat": [_U64, _U64, _I, _LL, _I, _U64, _U64],
     "ma_err_reduce": [_U64, _U64, _U64, _I, _LL, _I, _D, _U64, _I, _I, _U64],
@@ -84,6 +87,8 @@ def _declare_argtypes(lib: ctypes.CDLL) -> None:
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int
+    lib.ma_onepass_plan_destroy.argtypes = [_U64]
+    lib.ma_onepass_plan_destroy.restype = None
 
 
 def hip_available() -> bool:
@@ -1303,6 +1308,50 @@ def onepass_mode() -> int:
     return int(v) if v in ("0", "1", "2") else 1
 
 
+class _OnepassPlan:
+    """Native step plan of the one-pass update (``ma_onepass_plan_*``) with the
+    tensor objects whose addresses it holds. Destroyed with this object; a
+    copy or pickle of the owning metric gets None and builds its own."""
+
+    __slots__ = ("handle", "tensors", "scalars", "thr", "_destroy")
+
+    def __init__(self, lib, tensors, scalars, thr: Tensor):
+        scratch, tp, fp, tn, fn, confmat, correct, total, rowstats_buf, epoch_buf, hist, cs, _ = tensors
+        dt, C, T, ignore_index = scalars
+        uni, t0, inv_step = _uniform_params(thr)
+        rs_ptr = rowstats_buf.data_ptr()
+        handle = ctypes.c_ulonglong(0)
+        self.handle = 0
+        rc = lib.ma_onepass_plan_create(
+            dt, C, ignore_index if ignore_index is not None else 0,
+            1 if ignore_index is not None else 0,
+            scratch.data_ptr(), confmat.data_ptr() if confmat is not None else 0,
+            tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(),
+            correct.data_ptr() if correct is not None else 0,
+            total.data_ptr() if total is not None else 0,
+            rs_ptr, rs_ptr + 4 * rowstats_buf.shape[1], epoch_buf.data_ptr(),
+            thr.data_ptr(), T, uni, t0, inv_step, hist.data_ptr(), cs.data_ptr(),
+            ctypes.byref(handle),
+        )
+        _check(rc, "ma_onepass_plan_create")
+        self.handle = handle.value
+        self.tensors = tensors
+        self.scalars = scalars
+        self.thr = thr
+        self._destroy = lib.ma_onepass_plan_destroy
+
+    def __del__(self):
+        if self.handle:
+            self._destroy(self.handle)
+            self.handle = 0
+
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (type(None), ())
+
+
 def mc_onepass_update(
     preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int],
     stat, confmat: Optional[Tensor], exact, rowstats_buf: Tensor, epoch_buf: Tensor, curve,
@@ -1324,7 +1373,12 @@ def mc_onepass_update(
     """
     lib = _lib()
     C = num_classes
-    thr = curve.thresholds.contiguous().float()
+    plan = curve.__dict__.get("_hip_onepass_plan")
+    thr_src = curve.thresholds
+    if plan is not None and plan.tensors[-1] is thr_src:
+        thr = plan.thr
+    else:
+        thr = thr_src.contiguous().float()
     T = thr.numel()
     if not force and C < _ONEPASS_C_PER_T * T:
         return False
@@ -1342,27 +1396,29 @@ def mc_onepass_update(
     scratch, tp, fp, tn, fn = stat
     cs = curve.__dict__.get("_hip_onepass_scratch")
     if cs is None or cs.device != dev or cs.numel() != cs_words:
-        # [P | N1 | N0 copies | per-block records]; the tail kernel re-zeroes
-        # the counters, the records are overwritten every step
+        # [P | N1 | N0 copies | per-block records | per-block flags]; the tail
+        # kernel re-zeroes the counters, records and flags are overwritten
+        # every step
         cs = torch.zeros(cs_words, dtype=torch.long, device=dev)
         curve.__dict__["_hip_onepass_scratch"] = cs
     hist = _pooled_hist(C, T, dev, curve)
-    uni, t0, inv_step = _uniform_params(thr)
     assert curve.confmat.is_contiguous()
-    rs_ptr = rowstats_buf.data_ptr()
-    rc = lib.ma_mc_onepass_update(
-        _stream(), preds.data_ptr(), dt, target.data_ptr(), preds.shape[0], C,
-        ignore_index if ignore_index is not None else 0,
-        1 if ignore_index is not None else 0,
-        scratch.data_ptr(),
-        confmat.data_ptr() if confmat is not None else 0,
-        tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(),
-        exact[0].data_ptr() if exact is not None else 0,
-        exact[1].data_ptr() if exact is not None else 0,
-        rs_ptr, rs_ptr + 4 * rowstats_buf.shape[1], epoch_buf.data_ptr(),
-        thr.data_ptr(), T, uni, t0, inv_step, hist.data_ptr(), cs.data_ptr(),
+    # The native plan holds the addresses of everything that stays the same
+    # from step to step; the tensor OBJECTS are kept next to it, so none of the
+    # addresses can be freed or reused under the plan, and `is` on each of them
+    # (plus dtype, C, T, ignore_index) decides whether the plan still fits.
+    # reset() and a move to another device replace the state tensors: the next
+    # step rebuilds the plan. Until then one stale set of states stays alive.
+    tensors = (
+        scratch, tp, fp, tn, fn, confmat,
+        exact[0] if exact is not None else None, exact[1] if exact is not None else None,
+        rowstats_buf, epoch_buf, hist, cs, thr_src,
     )
-    _check(rc, "ma_mc_onepass_update")
+    scalars = (dt, C, T, ignore_index)
+    if plan is None or plan.scalars != scalars or not all(map(operator.is_, plan.tensors, tensors)):
+        plan = curve.__dict__["_hip_onepass_plan"] = _OnepassPlan(lib, tensors, scalars, thr)
+    rc = lib.ma_onepass_plan_step(plan.handle, _stream(), preds.data_ptr(), target.data_ptr(), preds.shape[0])
+    _check(rc, "ma_onepass_plan_step")
     if confmat is not None:
         _mark_kernel_mutated(confmat)
     _mark_kernel_mutated(tp)
