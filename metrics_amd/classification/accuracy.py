@@ -8,7 +8,7 @@ from torch import Tensor
 from metrics_amd.metric import Metric
 from metrics_amd.classification.base import _ClassificationTaskWrapper
 from metrics_amd.classification.stat_scores import BinaryStatScores, MulticlassStatScores, MultilabelStatScores
-from metrics_amd.functional.classification.accuracy import _accuracy_reduce
+from metrics_amd.functional.classification.accuracy import _accuracy_formula, _accuracy_reduce
 from metrics_amd.utilities.enums import ClassificationTask
 
 
@@ -44,6 +44,9 @@ class MulticlassAccuracy(MulticlassStatScores):
         return _accuracy_reduce(
             tp, fp, tn, fn, average=self.average, multidim_average=self.multidim_average, top_k=self.top_k
         )
+
+    def _compute_plan_spec(self):
+        return self._linear_plan_spec(_accuracy_formula(self.top_k))
 
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)

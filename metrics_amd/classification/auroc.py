@@ -86,6 +86,11 @@ class MulticlassAUROC(MulticlassPrecisionRecallCurve):
         state = (dim_zero_cat(self.preds), dim_zero_cat(self.target)) if self.thresholds is None else self.confmat
         return _multiclass_auroc_compute(state, self.num_classes, self.average, self.thresholds)
 
+    def _compute_plan_spec(self):
+        if self.thresholds is not None and self.average in ("macro", "weighted"):
+            return ("curve_auc", 0, self.average)
+        return None
+
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)
 

@@ -71,6 +71,11 @@ class MulticlassAveragePrecision(MulticlassPrecisionRecallCurve):
         state = (dim_zero_cat(self.preds), dim_zero_cat(self.target)) if self.thresholds is None else self.confmat
         return _multiclass_average_precision_compute(state, self.num_classes, self.average, self.thresholds)
 
+    def _compute_plan_spec(self):
+        if self.thresholds is not None and self.average in ("macro", "weighted"):
+            return ("curve_auc", 1, self.average)
+        return None
+
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)
 

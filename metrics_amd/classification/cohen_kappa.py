@@ -113,6 +113,9 @@ class MulticlassCohenKappa(Metric):
     def compute(self) -> Tensor:
         return _cohen_kappa_reduce(self.confmat, self.weights)
 
+    def _compute_plan_spec(self):
+        return ("confmat_scalar", 1) if self.weights is None else None
+
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)
 

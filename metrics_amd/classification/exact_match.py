@@ -99,6 +99,9 @@ class MulticlassExactMatch(Metric):
         correct = dim_zero_cat(self.correct) if isinstance(self.correct, list) else self.correct
         return _exact_match_reduce(correct, self.total)
 
+    def _compute_plan_spec(self):
+        return ("exact",) if self.multidim_average == "global" else None
+
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)
 

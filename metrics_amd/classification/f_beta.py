@@ -8,7 +8,7 @@ from torch import Tensor
 from metrics_amd.metric import Metric
 from metrics_amd.classification.base import _ClassificationTaskWrapper
 from metrics_amd.classification.stat_scores import BinaryStatScores, MulticlassStatScores, MultilabelStatScores
-from metrics_amd.functional.classification.f_beta import _fbeta_reduce
+from metrics_amd.functional.classification.f_beta import _fbeta_formula, _fbeta_reduce
 from metrics_amd.utilities.enums import ClassificationTask
 
 
@@ -98,6 +98,9 @@ class MulticlassFBetaScore(MulticlassStatScores):
             tp, fp, tn, fn, self.beta, average=self.average, multidim_average=self.multidim_average,
             zero_division=self.zero_division,
         )
+
+    def _compute_plan_spec(self):
+        return self._linear_plan_spec(_fbeta_formula(self.beta, self.zero_division))
 
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)

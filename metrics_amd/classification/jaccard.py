@@ -114,6 +114,12 @@ class MulticlassJaccardIndex(Metric):
     def compute(self) -> Tensor:
         return _jaccard_index_reduce(self.confmat, self.average, ignore_index=self.ignore_index, zero_division=self.zero_division)
 
+    def _compute_plan_spec(self):
+        ignored_class = self.ignore_index is not None and 0 <= self.ignore_index < self.num_classes
+        if self.average == "macro" and self.zero_division == 0.0 and not ignored_class:
+            return ("confmat_scalar", 2)
+        return None
+
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)
 

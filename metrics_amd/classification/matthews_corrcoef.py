@@ -107,6 +107,10 @@ class MulticlassMatthewsCorrCoef(Metric):
     def compute(self) -> Tensor:
         return _matthews_corrcoef_reduce(self.confmat)
 
+    def _compute_plan_spec(self):
+        # a 2 x 2 matrix takes the reducer's degenerate-binary branches
+        return ("confmat_scalar", 0) if self.num_classes != 2 else None
+
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)
 

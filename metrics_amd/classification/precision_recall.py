@@ -8,7 +8,7 @@ from torch import Tensor
 from metrics_amd.metric import Metric
 from metrics_amd.classification.base import _ClassificationTaskWrapper
 from metrics_amd.classification.stat_scores import BinaryStatScores, MulticlassStatScores, MultilabelStatScores
-from metrics_amd.functional.classification.precision_recall import _precision_recall_reduce
+from metrics_amd.functional.classification.precision_recall import _precision_recall_formula, _precision_recall_reduce
 from metrics_amd.utilities.enums import ClassificationTask
 
 
@@ -42,6 +42,9 @@ class MulticlassPrecision(MulticlassStatScores):
     def compute(self) -> Tensor:
         tp, fp, tn, fn = self._final_state()
         return _precision_recall_reduce("precision", tp, fp, tn, fn, average=self.average, multidim_average=self.multidim_average, top_k=self.top_k, zero_division=self.zero_division)
+
+    def _compute_plan_spec(self):
+        return self._linear_plan_spec(_precision_recall_formula("precision", self.top_k, self.zero_division))
 
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)
@@ -131,6 +134,9 @@ class MulticlassRecall(MulticlassStatScores):
     def compute(self) -> Tensor:
         tp, fp, tn, fn = self._final_state()
         return _precision_recall_reduce("recall", tp, fp, tn, fn, average=self.average, multidim_average=self.multidim_average, top_k=self.top_k, zero_division=self.zero_division)
+
+    def _compute_plan_spec(self):
+        return self._linear_plan_spec(_precision_recall_formula("recall", self.top_k, self.zero_division))
 
     def plot(self, val=None, ax=None):
         return self._plot(val, ax)

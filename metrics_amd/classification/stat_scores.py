@@ -222,6 +222,13 @@ class MulticlassStatScores(_AbstractStatScores):
         tp, fp, tn, fn = self._final_state()
         return _multiclass_stat_scores_compute(tp, fp, tn, fn, self.average, self.multidim_average)
 
+    def _linear_plan_spec(self, formula) -> Optional[tuple]:
+        """``_compute_plan_spec`` of the subclasses whose reducer is a linear
+        formula: the conditions under which that reducer takes the kernel."""
+        if self.multidim_average == "global" and self.average in ("micro", "macro", "weighted"):
+            return ("linear", formula, self.average)
+        return None
+
 
 class MultilabelStatScores(_AbstractStatScores):
     """Per-label tp/fp/tn/fn counts for multilabel tasks."""

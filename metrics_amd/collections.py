@@ -25,6 +25,7 @@ from torch.nn import ModuleDict
 
 from metrics_amd.metric import Metric
 from metrics_amd.utilities import tracing
+from metrics_amd.utilities.compute import _reduce_curve_auc
 from metrics_amd.utilities.data import _flatten_dict, allclose
 from metrics_amd.utilities.prints import rank_zero_warn
 
@@ -167,6 +168,173 @@ class _FusedMulticlassUpdatePlan:
         return handled
 
 
+class _FusedMulticlassComputePlan:
+    """Collection-level compute: every member that declares what it computes
+    (``Metric._compute_plan_spec``) over the stat-scores, confusion-matrix,
+    exact-match or threshold-curve group gets its result from ONE native call
+    of at most three launches (``csrc/mc_compute.hip``) instead of one Python
+    wrapper, cache lookup, allocation and launch per metric. The step also
+    performs the curve leader's lazy flush. Members it does not cover compute
+    on their own, as before."""
+
+    _STATES = {
+        "linear": ("tp", "fp", "tn", "fn"),
+        "confmat_scalar": ("confmat",),
+        "exact": ("correct", "total"),
+        "curve_auc": ("confmat",),
+    }
+    _KINDS = tuple(_STATES)
+
+    def __init__(self, leaders, members):
+        # kind -> leader metric; (metric, kind, spec, slot) per covered member:
+        # slot = index into the step's `out` buffer (curve: unused)
+        self.leaders = leaders
+        self.members = members
+        self.formulas = [p for m, kind, spec, _ in members if kind == "linear"
+                         for p in spec[1].params(spec[2])]
+        self.native = None
+        self.steps = 0
+
+    @classmethod
+    def build(cls, collection) -> "Optional[_FusedMulticlassComputePlan]":
+        leaders: dict = {}
+        covered: list = []
+        for names in collection._groups.values():
+            group = [getattr(collection, n) for n in names]
+            specs = [m._compute_plan_spec() for m in group]
+            kinds = {s[0] for s in specs if s is not None}
+            # one kind per group (its members share states) and one group per
+            # kind; whatever is left computes on its own
+            if len(kinds) != 1 or next(iter(kinds)) in leaders:
+                continue
+            leaders[kinds.pop()] = group[0]
+            covered += [(m, s) for m, s in zip(group, specs) if s is not None]
+        if not covered:
+            return None
+        # out = [linear 0..n-1 | mcc, kappa, jaccard | exact]
+        n_linear = sum(1 for _, s in covered if s[0] == "linear")
+        members, nxt = [], 0
+        for m, spec in covered:
+            kind = spec[0]
+            if kind == "linear":
+                slot, nxt = nxt, nxt + 1
+            elif kind == "confmat_scalar":
+                slot = n_linear + spec[1]
+            else:
+                slot = n_linear + 3
+            members.append((m, kind, spec, slot))
+        return cls(leaders, members)
+
+    def _state_tensors(self):
+        """The leaders' state tensors in the native plan's order, or None if a
+        state is not a tensor (list states) or the shapes do not fit one plan."""
+        out = []
+        for kind in self._KINDS:
+            leader = self.leaders.get(kind)
+            for name in self._STATES[kind]:
+                t = getattr(leader, name) if leader is not None else None
+                if leader is not None and not isinstance(t, Tensor):
+                    return None
+                out.append(t)
+        curve = self.leaders.get("curve_auc")
+        out.append(curve.__dict__.get("_hip_hist_buf") if curve is not None else None)
+        return tuple(out)
+
+    def _build_native(self, tensors):
+        from metrics_amd.ops import _hip
+
+        tp, fp, tn, fn, confmat, correct, total, curve_state, hist = tensors
+        present = [t for t in tensors if t is not None]
+        dev = present[0].device
+        if not all(t.is_cuda and t.device == dev and t.is_contiguous() and t.dtype == torch.long for t in present):
+            return None
+        sizes = set()
+        if tp is not None:
+            if tp.ndim != 1 or not (tp.shape == fp.shape == tn.shape == fn.shape):
+                return None
+            sizes.add(tp.numel())
+        if confmat is not None:
+            if confmat.ndim != 2 or confmat.shape[0] != confmat.shape[1]:
+                return None
+            sizes.add(confmat.shape[0])
+        if correct is not None and (correct.numel() != 1 or total.numel() != 1):
+            return None
+        T = 1
+        if curve_state is not None:
+            if curve_state.ndim != 4 or curve_state.shape[2:] != (2, 2):
+                return None
+            T, c = curve_state.shape[0], curve_state.shape[1]
+            if not _hip.curve_kernels_cover(T) or (hist is not None and hist.shape != (c, T + 1, 2)):
+                return None
+            sizes.add(c)
+        if len(sizes) > 1:
+            return None
+        C = sizes.pop() if sizes else 1
+        return _hip._ComputePlan(
+            dev, C, T, (tp, fp, tn, fn) if tp is not None else None, confmat,
+            (correct, total) if correct is not None else None,
+            (hist, curve_state) if curve_state is not None else None, self.formulas, 0.0,
+        )
+
+    def try_run(self) -> bool:
+        """Fill ``_computed`` of every covered member that has no cached result.
+        False: nothing was launched and nothing changed, the caller computes
+        every member as before."""
+        from metrics_amd.ops import _hip
+
+        if not (_hip.compute_plan_enabled() and _hip.hip_available()) or tracing.is_enabled():
+            return False
+        tensors = self._state_tensors()
+        if tensors is None:
+            return False
+        todo = []
+        dist: dict = {}  # distributed_available_fn -> its answer, asked once
+        for m, kind, spec, slot in self.members:
+            # every fast-path condition of Metric._wrap_compute; a member that
+            # wants a sync sends the whole collection down the old path
+            if m._is_synced or m.__dict__.get("_pending_sync_event") is not None:
+                return False
+            if m._to_sync:
+                fn = m.distributed_available_fn
+                if fn not in dist:
+                    dist[fn] = fn()
+                if dist[fn]:
+                    return False
+            if m._computed is not None or not m.compute_with_cache:
+                continue
+            leader = self.leaders[kind]
+            if m is not leader and not all(
+                getattr(m, name) is getattr(leader, name) for name in self._STATES[kind]
+            ):
+                continue  # not an alias of the leader's states: computes on its own
+            todo.append((m, kind, spec, slot))
+        if not todo:
+            return True
+        native = self.native
+        if native is None or not native.fits(tensors):
+            native = self.native = self._build_native(tensors)
+            if native is None:
+                return False
+        curve = self.leaders.get("curve_auc")
+        flush = False
+        if curve is not None and curve.__dict__.get("_lazy_dirty"):
+            C, T = tensors[7].shape[1], tensors[7].shape[0]
+            if curve.__dict__.get("_hip_lazy_meta") != (C, T, 1) or tensors[8] is None:
+                return False
+            curve.__dict__["_lazy_dirty"] = False  # the step is the flush
+            flush = True
+        out, auc = native.step(flush)
+        self.steps += 1
+        vals = out.unbind(0)
+        for m, kind, spec, slot in todo:
+            if kind == "curve_auc":
+                mode = spec[1]
+                m._computed = _reduce_curve_auc(auc[2 * mode], auc[2 * mode + 1], spec[2])  # fresh tensor
+            else:
+                m._computed = vals[slot]
+        return True
+
+
 class MetricCollection(ModuleDict):
     """A dict-like container of metrics sharing one ``update``/``compute`` call pattern.
 
@@ -192,6 +360,7 @@ class MetricCollection(ModuleDict):
     ) -> None:
         super().__init__()
         self._fused_plan: Any = False
+        self._compute_plan: Any = False
         self.prefix = self._check_arg(prefix, "prefix")
         self.postfix = self._check_arg(postfix, "postfix")
         self._enable_compute_groups = compute_groups
@@ -256,6 +425,13 @@ class MetricCollection(ModuleDict):
         return self._compute_and_reduce("compute")
 
     def _compute_and_reduce(self, method_name: str, *args: Any, **kwargs: Any) -> Dict[str, Any]:
+        if method_name == "compute" and self._groups_checked and not self._state_is_copy:
+            # one native call for every member that declared what it computes;
+            # their results land in `_computed`, which the loop below returns
+            if self._compute_plan is False:
+                self._compute_plan = _FusedMulticlassComputePlan.build(self)
+            if self._compute_plan is not None:
+                self._compute_plan.try_run()
         # lazy curve histograms live on group LEADERS; members alias the
         # leader's states and may compute first — materialize before iterating
         if self._groups_checked:
@@ -273,7 +449,7 @@ class MetricCollection(ModuleDict):
         _, duplicates = _flatten_dict(result)
 
         flat: Dict[str, Any] = {}
-        for k, m in self.items(keep_base=True, copy_state=False):
+        for k, m in self._modules.items():  # states were linked for the loop above
             res = result[k]
             if isinstance(res, dict):
                 for key, v in res.items():
@@ -346,14 +522,21 @@ class MetricCollection(ModuleDict):
             for members in self._groups.values():
                 getattr(self, members[0])._maybe_flush_lazy()
         if not self._state_is_copy:
+            modules = self._modules  # getattr(self, name) without Module.__getattr__
             for members in self._groups.values():
-                leader = getattr(self, members[0])
+                leader = modules[members[0]]
                 for name in members[1:]:
-                    member = getattr(self, name)
+                    member = modules[name]
                     for state in leader._defaults:
                         leader_state = getattr(leader, state)
-                        setattr(member, state, deepcopy(leader_state) if copy else leader_state)
-                    member._update_count = deepcopy(leader._update_count) if copy else leader._update_count
+                        if copy:
+                            setattr(member, state, deepcopy(leader_state))
+                        elif getattr(member, state) is not leader_state:
+                            # already linked is the steady state of every compute();
+                            # a Module setattr costs ten times the check
+                            setattr(member, state, leader_state)
+                    if copy or member._update_count != leader._update_count:
+                        member._update_count = deepcopy(leader._update_count) if copy else leader._update_count
         self._state_is_copy = copy
 
     @property
@@ -424,6 +607,7 @@ class MetricCollection(ModuleDict):
             )
 
         self._groups_checked = False
+        self._compute_plan = False
         if self._enable_compute_groups:
             self._init_compute_groups()
         else:

@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "compute_common.h"
 #include "curve_common.h"
 
 #define WAVE 64
@@ -703,80 +704,8 @@ __global__ void k_curve_suffix_tiled(
     unsigned long long* suf = shs + CTILE * (ll)(T + 1) * 2;  // CTILE * (T+1) * 2
     const ll c0 = (ll)blockIdx.x * CTILE;
     const int ctile = (int)min((ll)CTILE, C - c0);
-    for (int i = threadIdx.x; i < ctile * (T + 1) * 2; i += blockDim.x) {
-        const int lc = i / ((T + 1) * 2);
-        const int rem = i - lc * (T + 1) * 2;
-        stage[lc * (T + 1) * 2 + rem] = hist[(c0 + lc) * (ll)(T + 1) * 2 + rem];
-        if (zero_hist) hist[(c0 + lc) * (ll)(T + 1) * 2 + rem] = 0;
-    }
-    __syncthreads();
-    // wave-parallel per-class suffix scan: lane partials over T/64 chunks,
-    // cross-lane exclusive suffix via shfl, then a short serial tail per
-    // chunk — serial depth drops from O(T) to O(T/64)+log2(64)
-    {
-        const int lane = threadIdx.x & (WAVE - 1);
-        const int wv = threadIdx.x / WAVE;
-        const int nwaves = blockDim.x / WAVE;
-        const int chunk = (T + 1 + WAVE - 1) / WAVE;
-        for (int lc = wv; lc < ctile; lc += nwaves) {
-            unsigned long long* h = stage + lc * (T + 1) * 2;
-            unsigned long long* sf = suf + lc * (T + 1) * 2;
-            const int j0 = lane * chunk;
-            const int j1 = min(j0 + chunk, T + 1);
-            unsigned long long pf = 0, pt = 0;
-            for (int j = j0; j < j1; j++) { pf += h[j * 2 + 0]; pt += h[j * 2 + 1]; }
-            unsigned long long sfp = pf, stp = pt;  // inclusive suffix over lanes >= l
-            for (int off = 1; off < WAVE; off <<= 1) {
-                unsigned long long of = __shfl_down(sfp, off);
-                unsigned long long ot = __shfl_down(stp, off);
-                if (lane + off < WAVE) { sfp += of; stp += ot; }
-            }
-            unsigned long long run_f = sfp - pf;  // exclusive: sum over lanes > l
-            unsigned long long run_t = stp - pt;
-            for (int j = j1 - 1; j >= j0; j--) {
-                sf[j * 2 + 0] = run_f;  // sum over (j, T]
-                sf[j * 2 + 1] = run_t;
-                run_f += h[j * 2 + 0];
-                run_t += h[j * 2 + 1];
-            }
-            // lane 0's inclusive suffix is the grand total; slot 0 (never read
-            // as a suffix) stashes neg/pos totals — t=0 is reconstructed below
-            const unsigned long long tot_f = __shfl(sfp, 0);
-            const unsigned long long tot_t = __shfl(stp, 0);
-            if (lane == 0) { sf[0] = tot_f; sf[1] = tot_t; }
-        }
-    }
-    __syncthreads();
-    // wait: suffix for threshold t is sum over j > t, i.e. sf at j=t+1..T —
-    // the scan above stored, at position j, the sum over (j, T] EXCLUSIVE of
-    // j... no: at iteration j we stored the sum of elements j+1..T. So the
-    // confmat row t needs sf[t] as stored BEFORE adding h[t]? Position t
-    // holds sum over (t, T] = j > t. Correct as stored, except slot 0 was
-    // overwritten with totals — handle t=0 via totals minus h[0].
-    for (int i = threadIdx.x; i < T * ctile * 4; i += blockDim.x) {
-        const int t = i / (ctile * 4);
-        const int rem = i - t * (ctile * 4);
-        const int lc = rem >> 2;
-        const int q = rem & 3;
-        const unsigned long long* sf = suf + lc * (T + 1) * 2;
-        const unsigned long long* h = stage + lc * (T + 1) * 2;
-        const unsigned long long neg_total = sf[0];
-        const unsigned long long pos_total = sf[1];
-        unsigned long long fp_s, tp_s;
-        if (t == 0) {
-            fp_s = neg_total - h[0];
-            tp_s = pos_total - h[1];
-        } else {
-            fp_s = sf[t * 2 + 0];
-            tp_s = sf[t * 2 + 1];
-        }
-        ll v;
-        if (q == 0) v = (ll)(neg_total - fp_s);       // tn
-        else if (q == 1) v = (ll)fp_s;                // fp
-        else if (q == 2) v = (ll)(pos_total - tp_s);  // fn
-        else v = (ll)tp_s;                            // tp
-        confmat[((ll)t * C + (c0 + lc)) * 4 + q] += v;
-    }
+    // the tile body is shared with k_curve_flush_auc (compute_common.h)
+    curve_suffix_tile<CTILE, false>(hist, T, C, zero_hist, 1, confmat, stage, suf, c0, ctile);
     if (E && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&E[1], 1u);
 }
 
@@ -817,50 +746,7 @@ __global__ void k_confmat_scalars(
     unsigned long long* __restrict__ pk, const unsigned long long* __restrict__ diag,
     unsigned long long* __restrict__ tk /* consumed + re-zeroed */, ll C,
     float zero_division, float* __restrict__ out /* [mcc, kappa, jaccard_macro] */) {
-    __shared__ double sh[6][256];
-    double s_tot = 0, s_tr = 0, s_tkpk = 0, s_tk2 = 0, s_pk2 = 0;
-    double j_sum = 0, j_cnt = 0;
-    for (ll i = threadIdx.x; i < C; i += blockDim.x) {
-        const double t = (double)tk[i];
-        const double p = (double)pk[i];
-        const double d = (double)diag[i];
-        tk[i] = 0;  // scratch consumed: zero for the next call
-        pk[i] = 0;
-        s_tot += t;
-        s_tr += d;
-        s_tkpk += t * p;
-        s_tk2 += t * t;
-        s_pk2 += p * p;
-        const double den = t + p - d;
-        if (t + p > 0) {
-            j_cnt += 1.0;
-            j_sum += den > 0 ? d / den : (double)zero_division;
-        }
-    }
-    sh[0][threadIdx.x] = s_tot; sh[1][threadIdx.x] = s_tr; sh[2][threadIdx.x] = s_tkpk;
-    sh[3][threadIdx.x] = s_tk2; sh[4][threadIdx.x] = s_pk2; sh[5][threadIdx.x] = j_sum;
-    __shared__ double shc[256];
-    shc[threadIdx.x] = j_cnt;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) {
-            for (int q = 0; q < 6; q++) sh[q][threadIdx.x] += sh[q][threadIdx.x + off];
-            shc[threadIdx.x] += shc[threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        // float32 to match the torch reference chains bit-closely
-        const float s = (float)sh[0][0], c = (float)sh[1][0];
-        const float tkpk = (float)sh[2][0], tk2 = (float)sh[3][0], pk2 = (float)sh[4][0];
-        const float cov = c * s - tkpk;
-        const float den = (s * s - pk2) * (s * s - tk2);
-        out[0] = den == 0.0f ? 0.0f : cov / sqrtf(fmaxf(den, 1.1754944e-38f));
-        const float po_n = s - c;            // sum(w*cm),  w = 1 - I
-        const float pe_n = s - tkpk / s;     // sum(w*E)
-        out[1] = 1.0f - po_n / pe_n;         // 0/0 -> nan, x/0 -> inf: torch parity
-        out[2] = shc[0] > 0 ? (float)(sh[5][0] / shc[0]) : zero_division;
-    }
+    confmat_scalars_eval(pk, diag, tk, C, zero_division, out);
 }
 
 // single-thread epoch close for the lazy-confmat path (see ma_curve_epoch_bump)
@@ -935,86 +821,8 @@ __global__ void k_apply_stat_exact(
     }
 }
 
-// one-launch stat-score compute: every precision/recall/accuracy/F-beta/
-// specificity/NPV/hamming reduction is post(safe_div(n.s, d.s)) with linear
-// coefficients over (tp,fp,tn,fn), then micro / macro / weighted averaging —
-// ONE kernel replaces the ~15-launch torch chain per metric at compute time.
-// avg_mode: 0 macro, 1 weighted, 2 micro. Matches _adjust_weights_safe_divide
-// bit-for-bit: per-class (w*s)/W summed (not sum(w*s)/W).
-__device__ void _linear_stat_eval(
-    const ll* __restrict__ tp, const ll* __restrict__ fp, const ll* __restrict__ tn,
-    const ll* __restrict__ fn, ll C, float n0, float n1, float n2, float n3, float d0, float d1,
-    float d2, float d3, int avg_mode, int zero_w_topk, float zero_division, float post_a,
-    float post_b, float* __restrict__ out) {
-    __shared__ double red[256];
-    // pass 1: total weight W (macro/weighted) or nothing (micro)
-    double wsum = 0.0;
-    if (avg_mode != 2) {
-        for (ll i = threadIdx.x; i < C; i += blockDim.x) {
-            const float vtp = (float)tp[i], vfp = (float)fp[i], vfn = (float)fn[i];
-            if (avg_mode == 1) {
-                wsum += (double)(vtp + vfn);
-            } else {
-                const float empty = zero_w_topk ? (vtp + vfn) : (vtp + vfp + vfn);
-                wsum += (empty == 0.0f) ? 0.0 : 1.0;
-            }
-        }
-    }
-    red[threadIdx.x] = wsum;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    const float W = (float)red[0];
-    __syncthreads();
-
-    // pass 2: sum of per-class contributions, matching torch's
-    // _safe_divide(w*s, W).sum() element order: each term is (w*s)/W in f32
-    double a = 0.0, b = 0.0;
-    for (ll i = threadIdx.x; i < C; i += blockDim.x) {
-        const float vtp = (float)tp[i], vfp = (float)fp[i], vtn = (float)tn[i], vfn = (float)fn[i];
-        const float num = n0 * vtp + n1 * vfp + n2 * vtn + n3 * vfn;
-        const float den = d0 * vtp + d1 * vfp + d2 * vtn + d3 * vfn;
-        if (avg_mode == 2) {
-            a += (double)num;
-            b += (double)den;
-        } else {
-            const float s = post_a * (den != 0.0f ? num / den : zero_division) + post_b;
-            float w;
-            if (avg_mode == 1) {
-                w = vtp + vfn;
-            } else {
-                const float empty = zero_w_topk ? (vtp + vfn) : (vtp + vfp + vfn);
-                w = (empty == 0.0f) ? 0.0f : 1.0f;
-            }
-            a += (double)(W != 0.0f ? (w * s) / W : 0.0f);
-        }
-    }
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (avg_mode == 2) {
-        __shared__ double redb[256];
-        redb[threadIdx.x] = b;
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if (threadIdx.x < off) redb[threadIdx.x] += redb[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            const float fa = (float)red[0], fb = (float)redb[0];
-            out[0] = post_a * (fb != 0.0f ? fa / fb : zero_division) + post_b;
-        }
-    } else if (threadIdx.x == 0) {
-        out[0] = (float)red[0];
-    }
-}
-
-// batched variant: one block per formula over the SAME shared (C,) stat
+// one-launch stat-score compute (_linear_stat_eval, compute_common.h),
+// batched: one block per formula over the SAME shared (C,) stat
 // states — the 9 linear stat metrics of a compute group pay ONE dispatch per
 // compute generation instead of nine. params: 13 floats per formula
 // (n0-3, d0-3, avg_mode, zero_w_topk, zero_division, post_a, post_b).
@@ -1022,9 +830,7 @@ __global__ void k_linear_stat_multi(
     const ll* __restrict__ tp, const ll* __restrict__ fp, const ll* __restrict__ tn,
     const ll* __restrict__ fn, ll C, const float* __restrict__ params,
     float* __restrict__ outs) {
-    const float* P = params + (ll)blockIdx.x * 13;
-    _linear_stat_eval(tp, fp, tn, fn, C, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7],
-                      (int)P[8], (int)P[9], P[10], P[11], P[12], outs + blockIdx.x);
+    linear_stat_eval_params(tp, fp, tn, fn, C, params + (ll)blockIdx.x * 13, outs + blockIdx.x);
 }
 
 // per-class AUROC / AveragePrecision straight from the thresholded curve
@@ -1038,47 +844,14 @@ __global__ void k_curve_auc_from_confmat(
     float* __restrict__ out /* (C,) */, float* __restrict__ weights /* (C,) nullable */) {
     const ll c = blockIdx.x;
     __shared__ double red[256];
-    auto cm = [&](int t, int i, int j) -> float {
-        return (float)confmat[(((ll)t * C + c) * 2 + i) * 2 + j];
-    };
-    auto sdiv = [](float n, float d) -> float { return d != 0.0f ? n / d : 0.0f; };
-    double acc = 0.0;
-    if (mode == 0) {
-        for (int t = threadIdx.x; t < T - 1; t += blockDim.x) {
-            const float tp0 = cm(t, 1, 1), fn0 = cm(t, 1, 0), fp0 = cm(t, 0, 1), tn0 = cm(t, 0, 0);
-            const float tp1 = cm(t + 1, 1, 1), fn1 = cm(t + 1, 1, 0), fp1 = cm(t + 1, 0, 1),
-                        tn1 = cm(t + 1, 0, 0);
-            const float tpr0 = sdiv(tp0, tp0 + fn0), tpr1 = sdiv(tp1, tp1 + fn1);
-            const float fpr0 = sdiv(fp0, fp0 + tn0), fpr1 = sdiv(fp1, fp1 + tn1);
-            acc += (double)((fpr0 - fpr1) * 0.5f * (tpr0 + tpr1));
-        }
-    } else {
-        for (int t = threadIdx.x; t < T; t += blockDim.x) {
-            const float tp0 = cm(t, 1, 1), fn0 = cm(t, 1, 0), fp0 = cm(t, 0, 1);
-            const float p0 = sdiv(tp0, tp0 + fp0);
-            const float r0 = sdiv(tp0, tp0 + fn0);
-            float r1;
-            if (t + 1 < T) {
-                const float tp1 = cm(t + 1, 1, 1), fn1 = cm(t + 1, 1, 0);
-                r1 = sdiv(tp1, tp1 + fn1);
-            } else {
-                r1 = 0.0f;  // appended endpoint (recall_T = 0)
-            }
-            acc += (double)(-(r1 - r0) * p0);
-        }
-    }
-    red[threadIdx.x] = acc;
+    // integrands, slot order and tree are shared with k_curve_flush_auc
+    const CurveCmGlobal cm{confmat, C, c};
+    red[threadIdx.x] = curve_auc_slot_sum(cm, T, mode, (int)threadIdx.x);
     __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
+    tree256_block(red);
     if (threadIdx.x == 0) {
         out[c] = (float)red[0];
-        if (weights) {
-            const int tw = mode == 0 ? T - 1 : 0;
-            weights[c] = cm(tw, 1, 1) + cm(tw, 1, 0);
-        }
+        if (weights) weights[c] = curve_auc_weight(cm, T, mode);
     }
 }
 
@@ -1422,8 +1195,10 @@ int ma_linear_stat_multi(uintptr_t stream, uintptr_t tp, uintptr_t fp, uintptr_t
     return (int)hipGetLastError();
 }
 
-int ma_confmat_scalars(uintptr_t stream, uintptr_t cm, ll C, uintptr_t scratch /* 3C u64 */,
-                       float zero_division, uintptr_t out /* 3 f32 */) {
+// phase A of the confmat scalars alone (also launched by the collection
+// compute plan, mc_compute.hip): row sums, column sums, diagonal into the
+// pre-zeroed 3C u64 scratch [tk | pk | diag]
+int ma_confmat_moments(uintptr_t stream, uintptr_t cm, ll C, uintptr_t scratch /* 3C u64 */) {
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* tk = (unsigned long long*)scratch;
     unsigned long long* pk = tk + C;
@@ -1436,6 +1211,17 @@ int ma_confmat_scalars(uintptr_t stream, uintptr_t cm, ll C, uintptr_t scratch /
     row_tiles = (C + rows_per_block - 1) / rows_per_block;
     dim3 grid((unsigned)gx, (unsigned)row_tiles);
     k_confmat_moments<<<grid, 256, 0, s>>>((const ll*)cm, C, rows_per_block, tk, pk, diag);
+    return (int)hipGetLastError();
+}
+
+int ma_confmat_scalars(uintptr_t stream, uintptr_t cm, ll C, uintptr_t scratch /* 3C u64 */,
+                       float zero_division, uintptr_t out /* 3 f32 */) {
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* tk = (unsigned long long*)scratch;
+    unsigned long long* pk = tk + C;
+    unsigned long long* diag = pk + C;
+    const int rc = ma_confmat_moments(stream, cm, C, scratch);
+    if (rc != 0) return rc;
     k_confmat_scalars<<<1, 256, 0, s>>>(pk, diag, tk, C, zero_division, (float*)out);
     return (int)hipGetLastError();
 }

@@ -5,7 +5,7 @@ from typing import Optional
 
 from torch import Tensor
 
-from metrics_amd.utilities.compute import _adjust_weights_safe_divide, _safe_divide
+from metrics_amd.utilities.compute import LinearFormula, _adjust_weights_safe_divide, _safe_divide
 from metrics_amd.utilities.enums import ClassificationTask
 from metrics_amd.functional.classification.stat_scores import (
     _binary_stat_scores_arg_validation,
@@ -18,6 +18,12 @@ from metrics_amd.functional.classification.stat_scores import (
     _multilabel_stat_scores_pipeline,
     _multilabel_stat_scores_tensor_validation,
 )
+
+
+def _precision_recall_formula(stat: str, top_k: int = 1, zero_division: float = 0) -> LinearFormula:
+    """Multiclass precision = tp / (tp + fp), recall = tp / (tp + fn) per class."""
+    den = (1, 1, 0, 0) if stat == "precision" else (1, 0, 0, 1)
+    return LinearFormula((1, 0, 0, 0), den, top_k != 1, zero_division)
 
 
 def _precision_recall_reduce(
@@ -40,9 +46,8 @@ def _precision_recall_reduce(
         from metrics_amd.ops import _hip
 
         if _hip.hip_available():
-            den = (1, 1, 0, 0) if stat == "precision" else (1, 0, 0, 1)
             return _hip.linear_stat_compute(
-                tp, fp, tn, fn, (1, 0, 0, 0), den, average, top_k != 1, zero_division
+                tp, fp, tn, fn, _precision_recall_formula(stat, top_k, zero_division), average
             )
     if average == "binary":
         return _safe_divide(tp, tp + different_stat, zero_division)

@@ -5,7 +5,7 @@ from typing import Optional
 
 from torch import Tensor
 
-from metrics_amd.utilities.compute import _adjust_weights_safe_divide, _safe_divide
+from metrics_amd.utilities.compute import LinearFormula, _adjust_weights_safe_divide, _safe_divide
 from metrics_amd.utilities.enums import ClassificationTask
 from metrics_amd.functional.classification.stat_scores import (
     _binary_stat_scores_arg_validation,
@@ -18,6 +18,11 @@ from metrics_amd.functional.classification.stat_scores import (
     _multilabel_stat_scores_pipeline,
     _multilabel_stat_scores_tensor_validation,
 )
+
+
+def _specificity_formula() -> LinearFormula:
+    """Specificity = tn / (tn + fp) per class."""
+    return LinearFormula((0, 0, 1, 0), (0, 1, 1, 0))
 
 
 def _specificity_reduce(
@@ -36,7 +41,7 @@ def _specificity_reduce(
         from metrics_amd.ops import _hip
 
         if _hip.hip_available():
-            return _hip.linear_stat_compute(tp, fp, tn, fn, (0, 0, 1, 0), (0, 1, 1, 0), average)
+            return _hip.linear_stat_compute(tp, fp, tn, fn, _specificity_formula(), average)
     if average == "binary":
         return _safe_divide(tn, tn + fp)
     if average == "micro":

@@ -293,6 +293,20 @@ class Metric(Module, ABC):
             self.__dict__["_lazy_dirty"] = False
             self._lazy_flush()
 
+    def _compute_plan_spec(self) -> Optional[tuple]:
+        """What ``compute()`` evaluates, declared to the collection compute plan
+        (``collections._FusedMulticlassComputePlan``), or None if the metric
+        computes on its own. One of:
+
+        - ``("linear", LinearFormula, average)`` over the tp/fp/tn/fn states
+        - ``("confmat_scalar", k)`` over the (C, C) ``confmat`` state: k = 0
+          mcc, 1 unweighted kappa, 2 macro jaccard
+        - ``("exact",)`` over ``correct`` / ``total``
+        - ``("curve_auc", mode, average)`` over the (T, C, 2, 2) ``confmat``
+          state: mode 0 AUROC, 1 average precision
+        """
+        return None
+
     def forward(self, *args: Any, **kwargs: Any) -> Any:
         """Accumulate the batch into the global state AND return the batch value."""
         self._maybe_flush_lazy()

@@ -57,6 +57,9 @@ _SIGNATURES = {
     "ma_curve_suffix": [_U64, _U64, _LL, _I, _I, _I, _U64, _U64],
     "ma_curve_epoch_bump": [_U64, _U64],
     "ma_confmat_scalars": [_U64, _U64, _LL, _U64, ctypes.c_float, _U64],
+    "ma_confmat_moments": [_U64, _U64, _LL, _U64],
+    "ma_compute_plan_create": [_LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _F, _LL, ctypes.POINTER(ctypes.c_ulonglong)],
+    "ma_compute_plan_step": [_U64, _U64, _I, _U64, _U64],
     "ma_linear_stat_multi": [_U64, _U64, _U64, _U64, _U64, _LL, _I, _U64, _U64],
     "ma_apply_stat_deltas": [_U64, _U64, _LL, _U64, _U64, _U64, _U64, _U64],
     "ma_exact_apply": [_U64, _U64, _LL, _LL, _I, _U64, _U64],
@@ -89,6 +92,8 @@ def _declare_argtypes(lib: ctypes.CDLL) -> None:
         fn.restype = ctypes.c_int
     lib.ma_onepass_plan_destroy.argtypes = [_U64]
     lib.ma_onepass_plan_destroy.restype = None
+    lib.ma_compute_plan_destroy.argtypes = [_U64]
+    lib.ma_compute_plan_destroy.restype = None
 
 
 def hip_available() -> bool:
@@ -1166,28 +1171,19 @@ def mc_exact_into(
 _LINEAR_PLANS: dict = {}
 
 
-def linear_stat_compute(
-    tp: Tensor, fp: Tensor, tn: Tensor, fn: Tensor,
-    num_coefs, den_coefs, average: str, zero_w_topk: bool = False,
-    zero_division: float = 0.0, post_a: float = 1.0, post_b: float = 0.0,
-) -> Tensor:
+def linear_stat_compute(tp: Tensor, fp: Tensor, tn: Tensor, fn: Tensor, formula, average: str) -> Tensor:
     """One-launch linear-ratio stat reduction (precision/recall/accuracy/...).
 
-    score_c = post(safe_div(num_coefs . stats_c, den_coefs . stats_c)), then
-    micro / macro / weighted averaging exactly like
-    ``_adjust_weights_safe_divide``. Returns a 0-dim float32 tensor.
+    ``formula`` is the metric's :class:`~metrics_amd.utilities.compute.LinearFormula`:
+    score_c = post(safe_div(num . stats_c, den . stats_c)), then micro / macro /
+    weighted averaging exactly like ``_adjust_weights_safe_divide``. Returns a
+    0-dim float32 tensor.
     Formulas over the same state tensor are batched per compute generation:
     one grid launch evaluates all of them (see ``k_linear_stat_multi``).
     """
     lib = _lib()
     C = tp.numel()
-    avg_mode = {"macro": 0, "weighted": 1, "micro": 2}[average]
-    key = (
-        float(num_coefs[0]), float(num_coefs[1]), float(num_coefs[2]), float(num_coefs[3]),
-        float(den_coefs[0]), float(den_coefs[1]), float(den_coefs[2]), float(den_coefs[3]),
-        float(avg_mode), float(1 if zero_w_topk else 0),
-        float(zero_division), float(post_a), float(post_b),
-    )
+    key = formula.params(average)
     muts = _tensor_cache_get(_CONFMAT_MUTATIONS, tp)
     gen = (tp._version, muts[0] if muts is not None else 0)
     plan = _tensor_cache_get(_LINEAR_PLANS, tp)
@@ -1427,3 +1423,86 @@ def mc_onepass_update(
     curve.__dict__["_hip_lazy_meta"] = (C, T, 1)
     curve.__dict__["_lazy_dirty"] = True
     return True
+
+
+# Collection compute plan (csrc/mc_compute.hip). METRICS_AMD_COMPUTE_PLAN=0
+# turns it off: every member then computes through its own path, exactly as
+# before (A/B lever and the oracle of the tests). Read at every compute.
+COMPUTE_PLAN_ENV = "METRICS_AMD_COMPUTE_PLAN"
+COMPUTE_FLUSH = 1  # step flag: the curve histogram holds updates to flush
+
+
+def compute_plan_enabled() -> bool:
+    return os.environ.get(COMPUTE_PLAN_ENV, "1") != "0"
+
+
+class _ComputePlan:
+    """Native compute plan (``ma_compute_plan_*``) with the tensor objects
+    whose addresses it holds: ``tensors`` are the state tensors (``is`` on each
+    decides whether the plan still fits), ``owned`` the plan's own buffers.
+    Destroyed with this object; a copy or pickle gets None."""
+
+    __slots__ = ("handle", "tensors", "owned", "auc_views", "n_formulas", "auc_stride", "device", "_destroy")
+
+    def __init__(self, dev, C: int, T: int, stat, confmat, exact, curve, params, zero_division: float):
+        """stat = (tp, fp, tn, fn) | None, confmat = (C, C) state | None, exact =
+        (correct, total) | None, curve = (hist, (T, C, 2, 2) state) | None;
+        params = the 13 floats of every linear formula, flattened."""
+        lib = _lib()
+        self.device = dev
+        n = len(params) // 13
+        params_dev = torch.tensor(params, dtype=torch.float32, device=dev) if n else None
+        cm_scratch = torch.zeros(3 * C, dtype=torch.long, device=dev) if confmat is not None else None
+        # each per-class vector starts 256-byte aligned, as a fresh tensor does
+        self.auc_stride = (C + 63) // 64 * 64
+        auc = torch.empty(4, self.auc_stride, dtype=torch.float32, device=dev) if curve is not None else None
+        self.auc_views = tuple(auc[i, :C] for i in range(4)) if auc is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        st = stat if stat is not None else (None,) * 4
+        ex = exact if exact is not None else (None,) * 2
+        cv = curve if curve is not None else (None,) * 2
+        handle = ctypes.c_ulonglong(0)
+        self.handle = 0
+        rc = lib.ma_compute_plan_create(
+            C, T, ptr(st[0]), ptr(st[1]), ptr(st[2]), ptr(st[3]), ptr(confmat), ptr(cm_scratch),
+            ptr(ex[0]), ptr(ex[1]), ptr(cv[0]), ptr(cv[1]),
+            0,  # the lazy flush does not close an epoch: every update closed its own
+            ptr(params_dev), n, float(zero_division), self.auc_stride, ctypes.byref(handle),
+        )
+        _check(rc, "ma_compute_plan_create")
+        self.handle = handle.value
+        # the order of _FusedMulticlassComputePlan._state_tensors, which fits() gets
+        self.tensors = (*st, confmat, *ex, cv[1], cv[0])
+        self.owned = (params_dev, cm_scratch, auc)
+        self.n_formulas = n
+        self._destroy = lib.ma_compute_plan_destroy
+
+    def fits(self, tensors) -> bool:
+        return all(map(operator.is_, self.tensors, tensors))
+
+    def step(self, flush: bool):
+        """One native call, at most three launches. Returns (out, auc): a fresh
+        ``[linear 0..n-1 | mcc, kappa, jaccard | exact]`` float32 buffer and the
+        (C,) views ``(auroc, auroc weights, ap, ap weights)`` of the plan's own
+        per-class buffer (None without a curve group; overwritten by the next
+        step, so only reductions of them go to a caller)."""
+        auc = self.owned[2]
+        # fresh per compute: views of it go to the caller and are never recycled
+        out = torch.empty(self.n_formulas + 4, dtype=torch.float32, device=self.device)
+        rc = _lib().ma_compute_plan_step(
+            self.handle, _stream(), COMPUTE_FLUSH if flush else 0, out.data_ptr(),
+            auc.data_ptr() if auc is not None else 0,
+        )
+        _check(rc, "ma_compute_plan_step")
+        return out, self.auc_views
+
+    def __del__(self):
+        if self.handle:
+            self._destroy(self.handle)
+            self.handle = 0
+
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (type(None), ())

@@ -6,7 +6,7 @@ normalize_logits_if_needed).
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -55,6 +55,62 @@ def _adjust_weights_safe_divide(
         if not multilabel:
             weights[tp + fp + fn == 0 if top_k == 1 else tp + fn == 0] = 0.0
     return _safe_divide(weights * score, weights.sum(-1, keepdim=True)).sum(-1)
+
+
+_AVG_MODE = {"macro": 0, "weighted": 1, "micro": 2}
+
+
+class LinearFormula(NamedTuple):
+    """A stat-score reduction as the HIP kernels evaluate it:
+    ``post_a * safe_div(num . s, den . s, zero_division) + post_b`` with
+    ``s = (tp, fp, tn, fn)``, then micro / macro / weighted averaging as
+    ``_adjust_weights_safe_divide`` does (``zero_w_topk``: macro drops classes
+    with ``tp + fn == 0`` instead of ``tp + fp + fn == 0``).
+
+    The one statement of each metric's coefficients: the functional reducers
+    hand it to ``_hip.linear_stat_compute`` and the metric classes declare it to
+    the collection compute plan.
+    """
+
+    num: Tuple[float, float, float, float]
+    den: Tuple[float, float, float, float]
+    zero_w_topk: bool = False
+    zero_division: float = 0.0
+    post_a: float = 1.0
+    post_b: float = 0.0
+
+    def params(self, average: str) -> Tuple[float, ...]:
+        """The 13 floats per formula of ``k_linear_stat_multi``."""
+        return (
+            *(float(c) for c in self.num), *(float(c) for c in self.den),
+            float(_AVG_MODE[average]), float(1 if self.zero_w_topk else 0),
+            float(self.zero_division), float(self.post_a), float(self.post_b),
+        )
+
+    def evaluate(self, tp: Tensor, fp: Tensor, tn: Tensor, fn: Tensor, average: str) -> Tensor:
+        """The same reduction in plain torch."""
+        stats = [x.float() for x in (tp, fp, tn, fn)]
+        num = sum(c * x for c, x in zip(self.num, stats))
+        den = sum(c * x for c, x in zip(self.den, stats))
+        if average == "micro":
+            num, den = num.sum(-1), den.sum(-1)
+        score = self.post_a * _safe_divide(num, den, self.zero_division) + self.post_b
+        if average == "micro":
+            return score
+        return _adjust_weights_safe_divide(score, average, False, tp, fp, fn, 2 if self.zero_w_topk else 1)
+
+
+def _reduce_curve_auc(res: Tensor, weights: Tensor, average: Optional[str]) -> Optional[Tensor]:
+    """Average the per-class AUROC / AP vector of ``_hip.curve_auc_from_confmat``
+    (no NaNs: its safe divides return 0). None for an unknown ``average``."""
+    if average in (None, "none"):
+        return res
+    if average == "macro":
+        return res.mean()
+    if average == "weighted":
+        w = _safe_divide(weights, weights.sum())
+        return (res * w).sum()
+    return None
 
 
 def _auc_compute_without_check(x: Tensor, y: Tensor, direction: float, axis: int = -1) -> Tensor:
