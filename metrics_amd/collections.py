@@ -42,13 +42,21 @@ class _FusedMulticlassUpdatePlan:
     """Collection-level cross-metric fusion: the stat-scores, confusion-matrix
     and exact-match group leaders all start with the same argmax pass over the
     (B, C) logits — ONE fused kernel call feeds all of them (MI355X-first:
-    the logits are read once from HBM instead of three times)."""
+    the logits are read once from HBM instead of three times).
 
-    def __init__(self, stat, confmat, exact, curve):
+    ``topk`` is the leader of one stat-scores group with ``top_k > 1``: its
+    effective prediction is the target where the target ranks inside the top
+    k, else the same argmax, so the same pass counts it into a second scratch.
+    It is handled only by a step that really counted it (float logits, a class
+    count the slot covers); otherwise it updates on its own, as before."""
+
+    def __init__(self, stat, confmat, exact, curve, topk=None):
         self.stat = stat
         self.confmat = confmat
         self.exact = exact
         self.curve = curve
+        self.topk = topk
+        self.topk_steps = 0
         self.leaders = tuple(m for m in (stat, confmat, exact, curve) if m is not None)
         # one-pass step (logits read once); METRICS_AMD_ONEPASS=0 keeps the
         # stat + curve-hist + apply kernel sequence, 2 lifts the shape gate
@@ -61,15 +69,23 @@ class _FusedMulticlassUpdatePlan:
 
     @staticmethod
     def build(collection) -> "Optional[_FusedMulticlassUpdatePlan]":
-        stat = confmat = exact = curve = None
+        from metrics_amd.ops import _hip
+
+        stat = confmat = exact = curve = topk = None
+        fuse_topk = _hip.fuse_topk_enabled()
         for members in collection._groups.values():
             leader = getattr(collection, members[0])
             kind = getattr(type(leader), "_hip_fused_kind", None)
             if kind is None or getattr(leader, "validate_args", True):
                 continue  # validations are skipped on the fused path
-            if kind == "mc_stat" and stat is None:
-                if getattr(leader, "multidim_average", "global") == "global" and getattr(leader, "top_k", 1) == 1:
+            if kind == "mc_stat":
+                if getattr(leader, "multidim_average", "global") != "global":
+                    continue
+                top_k = getattr(leader, "top_k", 1)
+                if top_k == 1 and stat is None:
                     stat = leader
+                elif top_k > 1 and topk is None and fuse_topk and leader.num_classes is not None:
+                    topk = leader  # the first one; further top-k groups stay on their own
             elif kind == "mc_confmat" and confmat is None:
                 confmat = leader
             elif kind == "mc_exact" and exact is None:
@@ -78,8 +94,6 @@ class _FusedMulticlassUpdatePlan:
             elif kind == "mc_curve" and curve is None:
                 import os
 
-                from metrics_amd.ops import _hip
-
                 if (
                     leader.thresholds is not None
                     and _hip.curve_kernels_cover(leader.thresholds.numel())
@@ -87,14 +101,18 @@ class _FusedMulticlassUpdatePlan:
                     and os.environ.get("METRICS_AMD_FUSE_CURVE", "1") != "0"
                 ):
                     curve = leader
-        participants = [m for m in (stat, confmat, exact, curve) if m is not None]
-        if stat is None or len(participants) < 2:
+        if stat is None:
+            return None
+        if topk is not None and (topk.num_classes, topk.ignore_index) != (stat.num_classes, stat.ignore_index):
+            topk = None  # counts other rows or classes: it updates on its own
+        participants = [m for m in (stat, confmat, exact, curve, topk) if m is not None]
+        if len(participants) < 2:
             return None
         ncs = {m.num_classes for m in participants}
         igs = {m.ignore_index for m in participants}
         if len(ncs) != 1 or len(igs) != 1:
             return None
-        return _FusedMulticlassUpdatePlan(stat, confmat, exact, curve)
+        return _FusedMulticlassUpdatePlan(stat, confmat, exact, curve, topk)
 
     def try_run(self, *args: Any, **kwargs: Any) -> tuple:
         """Run the fused update if the inputs qualify; returns the handled
@@ -120,6 +138,18 @@ class _FusedMulticlassUpdatePlan:
         if scratch is None or scratch.device != preds.device:
             scratch = torch.zeros(3 * stat.num_classes + 1, dtype=torch.long, device=preds.device)
             stat._hip_scratch = scratch
+        # the top-k slot rides a step over float logits at a class count the
+        # stat kernel's slot covers (the one-pass kernel covers no smaller one)
+        topk = self.topk
+        slot = None
+        if topk is not None and preds.is_floating_point() and _hip.mc_stat_topk_covers(stat.num_classes):
+            scratch2 = getattr(topk, "_hip_scratch", None)
+            if scratch2 is None or scratch2.device != preds.device:
+                scratch2 = torch.zeros(3 * stat.num_classes, dtype=torch.long, device=preds.device)
+                topk._hip_scratch = scratch2
+            slot = (topk.top_k, scratch2, topk.tp, topk.fp, topk.tn, topk.fn)
+        else:
+            topk = None
         curve = self.curve
         rowstats = None
         if curve is not None and preds.is_floating_point():
@@ -137,9 +167,12 @@ class _FusedMulticlassUpdatePlan:
                 (scratch, stat.tp, stat.fp, stat.tn, stat.fn),
                 self.confmat.confmat if self.confmat is not None else None,
                 (self.exact.correct, self.exact.total) if self.exact is not None else None,
-                rbuf, ebuf, curve, self.onepass_force,
+                rbuf, ebuf, curve, self.onepass_force, slot,
             ):
                 self.onepass_steps += 1
+                if topk is not None:
+                    self.topk_steps += 1
+                    return (*self.leaders, topk)
                 return self.leaders
             rowstats = (rbuf[0], rbuf[1], ebuf)
         elif curve is not None:
@@ -155,6 +188,7 @@ class _FusedMulticlassUpdatePlan:
             # epoch for free (saves a dedicated ~4us bump dispatch per step)
             defer_apply=curve is not None,
             bump_epoch_ptr=rowstats[2].data_ptr() if curve is not None else 0,
+            topk=slot,
         )
         if curve is not None:
             _hip.curve_hist_into_confmat(
@@ -165,6 +199,9 @@ class _FusedMulticlassUpdatePlan:
             handled = self.leaders
         else:
             handled = tuple(m for m in self.leaders if m is not self.curve)
+        if topk is not None:
+            self.topk_steps += 1
+            handled = (*handled, topk)
         return handled
 
 

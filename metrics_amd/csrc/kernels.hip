@@ -45,13 +45,20 @@ typedef long long ll;
 // one wave per row; tp/fp/fn per class via global atomics; optional confmat.
 // Tie-break matches torch.argmax: lowest index wins.
 // ---------------------------------------------------------------------------
-template <typename T>
+// TOPK: the optional top-k stat slot of the fused collection step. The row's
+// effective prediction for the slot is the target if its logit ranks inside
+// the top k, else the argmax (row_fold.h, count_row_topk); the rank is counted
+// while the row streams by, against x[t] read before the loop. A template
+// parameter: without the slot this is the kernel it was before.
+template <typename T, bool TOPK = false>
 __global__ void __launch_bounds__(256) k_mc_stat_logits(
     const T* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
     int has_ignore, unsigned long long* __restrict__ tp, unsigned long long* __restrict__ fp,
     unsigned long long* __restrict__ fn, unsigned long long* __restrict__ confmat,
     unsigned long long* __restrict__ valid_count, ll* __restrict__ argmax_out,
-    float* __restrict__ rowmax, float* __restrict__ rowinv, unsigned int* __restrict__ E) {
+    float* __restrict__ rowmax, float* __restrict__ rowinv, unsigned int* __restrict__ E,
+    int topk = 0, unsigned long long* __restrict__ tp2 = nullptr,
+    unsigned long long* __restrict__ fp2 = nullptr, unsigned long long* __restrict__ fn2 = nullptr) {
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave_in_block = threadIdx.x / WAVE;
     const int waves_per_block = blockDim.x / WAVE;
@@ -72,6 +79,15 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
         ll best_idx = 0x7fffffffffffffffLL;
         float sm_m = -3.4e38f, sm_s = 0.0f;  // online softmax (max, sumexp)
         unsigned int row_out = 0;
+        // top-k slot: target and its logit before the row streams by (an
+        // out-of-range target reads nothing; its row is not counted)
+        ll tk = 0;
+        float xt = 0.0f;
+        unsigned int cnt = 0;
+        if constexpr (TOPK) {
+            tk = target[row];
+            if (tk >= 0 && tk < C) xt = ld_f32(prow, tk);
+        }
         // vectorized loads: 16B/lane for bf16 when C%8==0, else 8B/4B paths
         if (is_bf16_v<T> && (C & 7) == 0) {
             const bf16x8* pv = reinterpret_cast<const bf16x8*>(prow);
@@ -81,6 +97,7 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
                 unpack(pv[v], f);
                 if (want_stats) softmax_fold(f, sm_m, sm_s, row_out);
                 argmax_fold(f, v * 8, best, best_idx);
+                if constexpr (TOPK) rank_fold(f, v * 8, xt, tk, cnt);
             }
         } else if ((C & 3) == 0) {
             const vec4_t<T>* pv = reinterpret_cast<const vec4_t<T>*>(prow);
@@ -90,12 +107,14 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
                 unpack(pv[v], f);
                 if (want_stats) softmax_fold(f, sm_m, sm_s, row_out);
                 argmax_fold(f, v * 4, best, best_idx);
+                if constexpr (TOPK) rank_fold(f, v * 4, xt, tk, cnt);
             }
         } else {
             for (ll c = lane; c < C; c += WAVE) {
                 const float f[1] = {ld_f32(prow, c)};
                 if (want_stats) softmax_fold(f, sm_m, sm_s, row_out);
                 argmax_fold(f, c, best, best_idx);
+                if constexpr (TOPK) rank_fold(f, c, xt, tk, cnt);
             }
         }
         if (want_stats) {
@@ -103,6 +122,7 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
             if (lane == 0) { rowmax[row] = sm_m; rowinv[row] = 1.0f / sm_s; }
         }
         argmax_merge_wave(best, best_idx);
+        if constexpr (TOPK) cnt = wave_sum_u32(cnt);  // lane 0 holds the row's rank
         // the row's range bit lands in lane 0, which holds the target: an
         // ignored row takes no part in the softmax decision (reference order)
         const bool row_any_out = want_stats && __ballot(row_out != 0u) != 0ULL;
@@ -111,7 +131,10 @@ __global__ void __launch_bounds__(256) k_mc_stat_logits(
             const bool ignored = has_ignore && t == ignore_index;
             if (argmax_out) argmax_out[row] = best_idx;
             if (row_any_out && !ignored) outside = 1u;
-            if (count_row(t, best_idx, C, ignored, tp, fp, fn, confmat)) my_valid++;
+            if (count_row(t, best_idx, C, ignored, tp, fp, fn, confmat)) {
+                my_valid++;
+                if constexpr (TOPK) count_row_topk(t, best_idx, cnt, topk, tp2, fp2, fn2);
+            }
         }
     }
     // one valid-count atomic per block, not per row
@@ -793,11 +816,16 @@ __global__ void k_exact_apply(unsigned long long* __restrict__ scratch, ll C, ll
 // it (post-sync), so the whole scratch is consumed and re-zeroed in one launch
 // with no cross-block race and no host-side epochs — which also makes the
 // launch hipGraph-capturable.
+// TOPK: the same launch also applies the top-k slot's scratch [tp_k|fp_k|fn_k]
+// to its four states, with the same valid.
+template <bool TOPK>
 __global__ void k_apply_stat_exact(
     unsigned long long* __restrict__ scratch /* 3*C + 1 */, ll C, ll B,
     ll* __restrict__ tp, ll* __restrict__ fp, ll* __restrict__ tn, ll* __restrict__ fn,
     ll* __restrict__ correct /* nullable, with total */, ll* __restrict__ total,
-    unsigned int* __restrict__ E /* nullable: close the curve epoch here */) {
+    unsigned int* __restrict__ E /* nullable: close the curve epoch here */,
+    unsigned long long* __restrict__ scratch2 /* 3*C, TOPK only */, ll* __restrict__ tp2,
+    ll* __restrict__ fp2, ll* __restrict__ tn2, ll* __restrict__ fn2) {
     if (E && threadIdx.x == 0) E[1] += 1u;
     __shared__ unsigned long long part[256];
     __shared__ unsigned long long valid_s;
@@ -806,8 +834,10 @@ __global__ void k_apply_stat_exact(
     const ll valid = (ll)valid_s;
     if (threadIdx.x == 0) scratch[3 * C] = 0;
     unsigned long long acc = 0;
-    for (ll i = threadIdx.x; i < C; i += blockDim.x)
+    for (ll i = threadIdx.x; i < C; i += blockDim.x) {
         acc += (unsigned long long)apply_stat_class(scratch, C, i, valid, tp, fp, tn, fn);
+        if constexpr (TOPK) apply_stat_class(scratch2, C, i, valid, tp2, fp2, tn2, fn2);
+    }
     if (!correct) return;  // block-uniform
     part[threadIdx.x] = acc;
     __syncthreads();
@@ -974,7 +1004,58 @@ static inline int grid_for(ll n, int block) {
     return (int)g;
 }
 
+// rows per wave of k_mc_stat_logits (MA_STAT_DIV) and the largest C of the
+// thread-per-row kernel (MA_STAT_SMALLC), each read once
+static int mc_stat_rows_div() {
+    static int rows_div = 0;
+    if (rows_div == 0) {
+        const char* e = getenv("MA_STAT_DIV");
+        rows_div = e ? atoi(e) : 16;
+        if (rows_div < 4) rows_div = 4;
+    }
+    return rows_div;
+}
+static int mc_stat_smallc() {
+    static int smallc = -1;
+    if (smallc < 0) {
+        const char* e = getenv("MA_STAT_SMALLC");
+        smallc = e ? atoi(e) : 128;
+    }
+    return smallc;
+}
+
 extern "C" {
+
+// whether ma_mc_stat_logits_topk covers C classes: the thread-per-row kernel
+// for small C has no top-k slot
+int ma_mc_stat_topk_covers(ll C) { return C > mc_stat_smallc() ? 1 : 0; }
+
+// ma_mc_stat_logits with the top-k slot: also counts, per valid row, the
+// effective prediction "target if it ranks inside the top k, else the argmax"
+// into tp2/fp2/fn2 ((C,) u64 each). -103 where the slot is not covered.
+int ma_mc_stat_logits_topk(uintptr_t stream, uintptr_t preds, int dtype /*0=f32 1=bf16*/,
+                           uintptr_t target, ll B, ll C, ll ignore_index, int has_ignore,
+                           uintptr_t tp, uintptr_t fp, uintptr_t fn, uintptr_t confmat,
+                           uintptr_t valid_count, uintptr_t argmax_out, uintptr_t rowmax,
+                           uintptr_t rowinv, uintptr_t epoch_buf, int k, uintptr_t tp2,
+                           uintptr_t fp2, uintptr_t fn2) {
+    typedef unsigned long long ull;
+    hipStream_t s = (hipStream_t)stream;
+    if (!ma_mc_stat_topk_covers(C) || k < 1 || !tp2 || !fp2 || !fn2) return -103;
+    const int grid = grid_for(B, mc_stat_rows_div());
+    if (dtype == 0)
+        k_mc_stat_logits<float, true><<<grid, 256, 0, s>>>(
+            (const float*)preds, (const ll*)target, B, C, ignore_index, has_ignore, (ull*)tp,
+            (ull*)fp, (ull*)fn, (ull*)confmat, (ull*)valid_count, (ll*)argmax_out, (float*)rowmax,
+            (float*)rowinv, (unsigned int*)epoch_buf, k, (ull*)tp2, (ull*)fp2, (ull*)fn2);
+    else
+        k_mc_stat_logits<unsigned short, true><<<grid, 256, 0, s>>>(
+            (const unsigned short*)preds, (const ll*)target, B, C, ignore_index, has_ignore,
+            (ull*)tp, (ull*)fp, (ull*)fn, (ull*)confmat, (ull*)valid_count, (ll*)argmax_out,
+            (float*)rowmax, (float*)rowinv, (unsigned int*)epoch_buf, k, (ull*)tp2, (ull*)fp2,
+            (ull*)fn2);
+    return (int)hipGetLastError();
+}
 
 int ma_mc_stat_logits(uintptr_t stream, uintptr_t preds, int dtype /*0=f32 1=bf16*/,
                       uintptr_t target, ll B, ll C, ll ignore_index, int has_ignore, uintptr_t tp,
@@ -988,19 +1069,9 @@ int ma_mc_stat_logits(uintptr_t stream, uintptr_t preds, int dtype /*0=f32 1=bf1
         (unsigned int*)epoch_buf
     // each wave loops several rows: more vector loads in flight per lane
     // (latency-bound otherwise; sweep tools/curve_sweep.py analogue)
-    static int rows_div = 0;
-    if (rows_div == 0) {
-        const char* e = getenv("MA_STAT_DIV");
-        rows_div = e ? atoi(e) : 16;
-        if (rows_div < 4) rows_div = 4;
-    }
+    const int rows_div = mc_stat_rows_div();
     // small-C: thread-per-row variant (wave-per-row wastes (64-C)/64 lanes)
-    static int smallc = -1;
-    if (smallc < 0) {
-        const char* e = getenv("MA_STAT_SMALLC");
-        smallc = e ? atoi(e) : 128;
-    }
-    if (C <= smallc) {
+    if (C <= mc_stat_smallc()) {
         int grid = grid_for(B, 256);
         if (grid > 4096) grid = 4096;
         const size_t shmem = (size_t)(3 * C + (confmat && C <= 64 ? C * C : 0)) * sizeof(unsigned int);
@@ -1235,10 +1306,36 @@ int ma_curve_epoch_bump(uintptr_t stream, uintptr_t epoch_buf) {
 int ma_apply_stat_deltas(uintptr_t stream, uintptr_t scratch, ll C, uintptr_t tp,
                          uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t epoch_buf) {
     hipStream_t s = (hipStream_t)stream;
-    k_apply_stat_exact<<<1, 256, 0, s>>>((unsigned long long*)scratch, C, 0, (ll*)tp, (ll*)fp,
-                                         (ll*)tn, (ll*)fn, nullptr, nullptr,
-                                         (unsigned int*)epoch_buf);
+    k_apply_stat_exact<false><<<1, 256, 0, s>>>((unsigned long long*)scratch, C, 0, (ll*)tp,
+                                                (ll*)fp, (ll*)tn, (ll*)fn, nullptr, nullptr,
+                                                (unsigned int*)epoch_buf, nullptr, nullptr,
+                                                nullptr, nullptr, nullptr);
     return (int)hipGetLastError();
+}
+
+// ma_apply_stat_exact with the top-k slot: the same single launch also applies
+// scratch2 = [tp_k|fp_k|fn_k] (3*C u64, consumed and zeroed) to tp2/fp2/tn2/fn2
+// with the same valid. correct/total may be 0, as in ma_apply_stat_deltas.
+int ma_apply_stat_exact_topk(uintptr_t stream, uintptr_t scratch, ll C, ll B, uintptr_t tp,
+                             uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t correct,
+                             uintptr_t total, uintptr_t epoch_buf, uintptr_t scratch2,
+                             uintptr_t tp2, uintptr_t fp2, uintptr_t tn2, uintptr_t fn2) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!scratch2 || !tp2 || !fp2 || !tn2 || !fn2) return -103;
+    k_apply_stat_exact<true><<<1, 256, 0, s>>>((unsigned long long*)scratch, C, B, (ll*)tp,
+                                               (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct, (ll*)total,
+                                               (unsigned int*)epoch_buf,
+                                               (unsigned long long*)scratch2, (ll*)tp2, (ll*)fp2,
+                                               (ll*)tn2, (ll*)fn2);
+    return (int)hipGetLastError();
+}
+
+int ma_apply_stat_deltas_topk(uintptr_t stream, uintptr_t scratch, ll C, uintptr_t tp,
+                              uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t epoch_buf,
+                              uintptr_t scratch2, uintptr_t tp2, uintptr_t fp2, uintptr_t tn2,
+                              uintptr_t fn2) {
+    return ma_apply_stat_exact_topk(stream, scratch, C, 0, tp, fp, tn, fn, 0, 0, epoch_buf,
+                                    scratch2, tp2, fp2, tn2, fn2);
 }
 
 int ma_curve_auc_from_confmat(uintptr_t stream, uintptr_t confmat, int T, ll C, int mode,
@@ -1253,9 +1350,10 @@ int ma_apply_stat_exact(uintptr_t stream, uintptr_t scratch, ll C, ll B, uintptr
                         uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t correct,
                         uintptr_t total, uintptr_t epoch_buf) {
     hipStream_t s = (hipStream_t)stream;
-    k_apply_stat_exact<<<1, 256, 0, s>>>((unsigned long long*)scratch, C, B, (ll*)tp, (ll*)fp,
-                                         (ll*)tn, (ll*)fn, (ll*)correct, (ll*)total,
-                                         (unsigned int*)epoch_buf);
+    k_apply_stat_exact<false><<<1, 256, 0, s>>>((unsigned long long*)scratch, C, B, (ll*)tp,
+                                                (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct,
+                                                (ll*)total, (unsigned int*)epoch_buf, nullptr,
+                                                nullptr, nullptr, nullptr, nullptr);
     return (int)hipGetLastError();
 }
 

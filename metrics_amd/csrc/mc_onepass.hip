@@ -18,6 +18,13 @@
 //           argmax_merge_wave. Both implement one exact rule — largest
 //           non-NaN value, lowest index on a tie — so the counts agree by
 //           specification (tests/unittests/gpu/test_row_argmax_edges.py).
+//           TOP-K SLOT (template parameter TOPK, optional): a second stat
+//           group whose effective prediction is the target if its logit ranks
+//           inside the top k, else the argmax. Only the rank is missing: x[t]
+//           comes out of the registers that hold the row (row_element), one
+//           compare-and-count over the unpacked values and one wave sum give
+//           it, lane 0 counts into a second scratch next to count_row, the
+//           tail applies that scratch with the same valid.
 //  phase B  CERTAINTY RULE: if this row itself holds an element outside
 //           [0,1], the batch-global answer is already known to be "softmax",
 //           and the row is binned from registers right away. A row with every
@@ -82,14 +89,18 @@ typedef unsigned long long ull;
 #define ONEPASS_CS_WORDS(C) (ONEPASS_FLAG_OFF(C) + ONEPASS_GRID_MAX / 8)
 #define ONEPASS_TAIL_GRID_DEFAULT 4096  // blocks of k_onepass_tail, see ma_mc_onepass_update
 
-template <typename T_, int NV>
+// TOPK: the optional top-k stat slot (second scratch tp2|fp2|fn2, see
+// count_row_topk). A template parameter, so the instantiation without the slot
+// is the kernel it was before the slot existed.
+template <typename T_, int NV, bool TOPK>
 __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_onepass(
     const uint4* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
     int has_ignore, ull* __restrict__ tp, ull* __restrict__ fp, ull* __restrict__ fn,
     ull* __restrict__ confmat, float* __restrict__ rowmax, float* __restrict__ rowinv,
     const float* __restrict__ thresholds, int T, int uniform, float t0, float inv_step,
     ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cs /* [P|N1|N0 copies] */,
-    uint4* __restrict__ records /* gridDim.x */, unsigned char* __restrict__ flags /* gridDim.x */) {
+    uint4* __restrict__ records /* gridDim.x */, unsigned char* __restrict__ flags /* gridDim.x */,
+    int topk, ull* __restrict__ tp2, ull* __restrict__ fp2, ull* __restrict__ fn2 /* TOPK only */) {
     constexpr int EPV = 16 / sizeof(T_);  // elements per 16-byte vector
     extern __shared__ float sthr[];
     __shared__ unsigned int block_valid, blk_outside, blk_binned, blk_deferred, blk_correct;
@@ -163,11 +174,33 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
         const float rinv = 1.0f / rsum;
         const bool certain = __ballot(row_out != 0u) != 0ULL;  // this row alone proves "softmax"
         const bool bin_now = certain && !ignored;
+        // ---- top-k slot: rank of x[t] among the row, from the registers ----
+        // Needed only for a valid row whose argmax is not the target (a == t
+        // means rank 0); both are wave-uniform, so the count is skipped
+        // otherwise and lane 0 sees rank 0, which gives the same counts.
+        unsigned int rank = 0;
+        if constexpr (TOPK) {
+            if (!ignored && t >= 0 && t < C && best_idx < (unsigned int)C && (ll)best_idx != t) {
+                const float xt = row_element<T_, NV>(r, (int)t);
+                unsigned int cnt = 0;
+#pragma unroll
+                for (int k = 0; k < NV; k++) {
+                    const int v = lane + k * WAVE;
+                    if (v < nvec) {
+                        float f[EPV];
+                        unpack16<T_>(r[k], f);
+                        rank_fold(f, v * EPV, xt, (int)t, cnt);
+                    }
+                }
+                rank = wave_sum_u32(cnt);  // lane 0 holds the row's rank
+            }
+        }
         if (lane == 0) {
             const ll p = (ll)best_idx;
             if (count_row(t, p, C, ignored, tp, fp, fn, confmat)) {
                 my_valid++;
                 if (p == t) my_correct++;
+                if constexpr (TOPK) count_row_topk(t, p, rank, topk, tp2, fp2, fn2);
             }
             rowmax[row] = rmax;
             rowinv[row] = (bin_now || ignored) ? -rinv : rinv;
@@ -287,7 +320,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
 //      over the (class-chunk, 256-row) tiles of the deferred pass.
 // Nothing written by one block is read by another; there is no ticket, spin
 // or grid-wide wait.
-template <typename T_>
+template <typename T_, bool TOPK>
 __global__ void __launch_bounds__(256) k_onepass_tail(
     const uint4* __restrict__ records, const unsigned char* __restrict__ flags,
     int grid /* blocks k_mc_onepass ran with */,
@@ -297,7 +330,8 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     const float* __restrict__ thresholds, int T, ull* __restrict__ hist /* (C, T+1, 2) */,
     const T_* __restrict__ probs, const ll* __restrict__ target, ll ignore_index, int has_ignore,
     int uniform, float t0, float inv_step, int c_chunk, const float* __restrict__ rowmax,
-    const float* __restrict__ rowinv) {
+    const float* __restrict__ rowinv, ull* __restrict__ scratch2 /* 3*C, TOPK only */,
+    ll* __restrict__ tp2, ll* __restrict__ fp2, ll* __restrict__ tn2, ll* __restrict__ fn2) {
     extern __shared__ float sthr_t[];  // a global-memory binary search is ~8 dependent misses
     __shared__ unsigned int wsum[256 / WAVE][5];
     const int lane = threadIdx.x & (WAVE - 1);
@@ -344,6 +378,8 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     const ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < C) {
         apply_stat_class(scratch, C, i, valid, tp, fp, tn, fn);
+        // the top-k slot: the same valid, its own scratch and states
+        if constexpr (TOPK) apply_stat_class(scratch2, C, i, valid, tp2, fp2, tn2, fn2);
         if (binned) {  // no row binned => the three counters are already zero
             const int b0 = bucket_of(0.0f, sthr_t, T);
             const ll P = (ll)cs[i];
@@ -468,24 +504,54 @@ struct OnepassPlan {
     float *rowmax, *rowinv;
     unsigned int* epoch_buf;
     const float* thresholds;
+    // top-k stat slot (ma_onepass_plan_set_topk); topk == 0: no slot
+    int topk;
+    ull* scratch2;  // [tp_k|fp_k|fn_k], 3*C u64
+    ll *tp2, *fp2, *tn2, *fn2;
 };
 
-template <typename T_, int NV>
+template <typename T_, int NV, bool TOPK>
 static void onepass_launch_main(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
                                 const ll* target, ll B, uint4* records, unsigned char* flags) {
     ull* sc = p.scratch;
-    k_mc_onepass<T_, NV><<<grid, 256, (size_t)p.T * sizeof(float), s>>>(
+    ull* sc2 = TOPK ? p.scratch2 : nullptr;
+    k_mc_onepass<T_, NV, TOPK><<<grid, 256, (size_t)p.T * sizeof(float), s>>>(
         (const uint4*)preds, target, B, p.C, p.ignore_index, p.has_ignore, sc, sc + p.C,
         sc + 2 * p.C, p.confmat, p.rowmax, p.rowinv, p.thresholds, p.T, p.uniform, p.t0,
-        p.inv_step, p.hist, p.cscratch, records, flags);
+        p.inv_step, p.hist, p.cscratch, records, flags, p.topk, sc2, TOPK ? sc2 + p.C : nullptr,
+        TOPK ? sc2 + 2 * p.C : nullptr);
 }
-template <typename T_>
+template <typename T_, bool TOPK>
 static void onepass_launch_nv(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
                               const ll* target, ll B, uint4* records, unsigned char* flags) {
-    if (p.nv == 1) onepass_launch_main<T_, 1>(p, s, grid, preds, target, B, records, flags);
-    else if (p.nv == 2) onepass_launch_main<T_, 2>(p, s, grid, preds, target, B, records, flags);
-    else if (p.nv == 4) onepass_launch_main<T_, 4>(p, s, grid, preds, target, B, records, flags);
-    else onepass_launch_main<T_, 8>(p, s, grid, preds, target, B, records, flags);
+    if (p.nv == 1) onepass_launch_main<T_, 1, TOPK>(p, s, grid, preds, target, B, records, flags);
+    else if (p.nv == 2) onepass_launch_main<T_, 2, TOPK>(p, s, grid, preds, target, B, records, flags);
+    else if (p.nv == 4) onepass_launch_main<T_, 4, TOPK>(p, s, grid, preds, target, B, records, flags);
+    else onepass_launch_main<T_, 8, TOPK>(p, s, grid, preds, target, B, records, flags);
+}
+template <typename T_, bool TOPK>
+static void onepass_launch_tail(const OnepassPlan& p, hipStream_t s, int tgrid, int grid,
+                                const void* preds, const ll* target, ll B, int c_chunk,
+                                const uint4* records, const unsigned char* flags) {
+    k_onepass_tail<T_, TOPK><<<tgrid, 256, (size_t)p.T * sizeof(float), s>>>(
+        records, flags, grid, p.scratch, p.C, B, p.tp, p.fp, p.tn, p.fn, p.correct, p.total,
+        p.epoch_buf, p.cscratch, p.thresholds, p.T, p.hist, (const T_*)preds, target,
+        p.ignore_index, p.has_ignore, p.uniform, p.t0, p.inv_step, c_chunk,
+        (const float*)p.rowmax, (const float*)p.rowinv, p.scratch2, p.tp2, p.fp2, p.tn2, p.fn2);
+}
+// the dtype and slot dispatch of both kernels, written once
+template <bool TOPK>
+static void onepass_launch_main_dt(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
+                                   const ll* target, ll B, uint4* records, unsigned char* flags) {
+    if (p.dtype == 0) onepass_launch_nv<float, TOPK>(p, s, grid, preds, target, B, records, flags);
+    else onepass_launch_nv<unsigned short, TOPK>(p, s, grid, preds, target, B, records, flags);
+}
+template <bool TOPK>
+static void onepass_launch_tail_dt(const OnepassPlan& p, hipStream_t s, int tgrid, int grid,
+                                   const void* preds, const ll* target, ll B, int c_chunk,
+                                   const uint4* records, const unsigned char* flags) {
+    if (p.dtype == 0) onepass_launch_tail<float, TOPK>(p, s, tgrid, grid, preds, target, B, c_chunk, records, flags);
+    else onepass_launch_tail<unsigned short, TOPK>(p, s, tgrid, grid, preds, target, B, c_chunk, records, flags);
 }
 
 // The whole fused-collection step on one stream in two launches: one-pass
@@ -499,8 +565,8 @@ static int onepass_step(const OnepassPlan& p, hipStream_t s, uintptr_t preds, ui
     unsigned char* flags = (unsigned char*)(p.cscratch + ONEPASS_FLAG_OFF(C));
     const int grid = B > 0 ? onepass_grid(B) : 0;
     if (B > 0) {
-        if (p.dtype == 0) onepass_launch_nv<float>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
-        else onepass_launch_nv<unsigned short>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
+        if (p.topk > 0) onepass_launch_main_dt<true>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
+        else onepass_launch_main_dt<false>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -523,11 +589,8 @@ static int onepass_step(const OnepassPlan& p, hipStream_t s, uintptr_t preds, ui
     const ll eblocks = (C + 255) / 256;
     if (tg < eblocks) tg = eblocks;
     const int tgrid = (int)((tg + 7) / 8 * 8);  // multiple of 8: block % 8 is the XCD
-    LAUNCH_BY_DTYPE(p.dtype, k_onepass_tail, tgrid, 256, (size_t)p.T * sizeof(float), s, records,
-                    flags, grid, p.scratch, C, B, p.tp, p.fp, p.tn, p.fn, p.correct, p.total, p.epoch_buf,
-                    p.cscratch, p.thresholds, p.T, p.hist, (const DT*)preds, (const ll*)target,
-                    p.ignore_index, p.has_ignore, p.uniform, p.t0, p.inv_step, c_chunk,
-                    (const float*)p.rowmax, (const float*)p.rowinv);
+    if (p.topk > 0) onepass_launch_tail_dt<true>(p, s, tgrid, grid, (const void*)preds, (const ll*)target, B, c_chunk, records, flags);
+    else onepass_launch_tail_dt<false>(p, s, tgrid, grid, (const void*)preds, (const ll*)target, B, c_chunk, records, flags);
     return (int)hipGetLastError();
 }
 
@@ -555,6 +618,7 @@ static int onepass_plan_fill(OnepassPlan& p, int dtype, ll C, ll ignore_index, i
     p.correct = (ll*)correct; p.total = (ll*)total;
     p.rowmax = (float*)rowmax; p.rowinv = (float*)rowinv;
     p.epoch_buf = (unsigned int*)epoch_buf; p.thresholds = (const float*)thresholds;
+    p.topk = 0; p.scratch2 = nullptr; p.tp2 = p.fp2 = p.tn2 = p.fn2 = nullptr;
     return 0;
 }
 
@@ -575,6 +639,25 @@ int ma_onepass_plan_create(int dtype, ll C, ll ignore_index, int has_ignore, uin
                                      thresholds, T, uniform, t0, inv_step, hist, cscratch);
     if (rc != 0) { delete p; return rc; }
     *handle = (unsigned long long)(uintptr_t)p;
+    return 0;
+}
+
+// Give a plan the top-k stat slot: every later step also counts, per valid row,
+// the effective prediction "target if it ranks inside the top k, else the
+// argmax" into scratch2 = [tp_k|fp_k|fn_k] (3*C u64, zero before the first step
+// and zero again after every tail) and applies it to the four states. k == 0
+// takes the slot away again. -103 for k < 0 or a missing buffer.
+int ma_onepass_plan_set_topk(uintptr_t handle, int k, uintptr_t scratch2, uintptr_t tp2,
+                             uintptr_t fp2, uintptr_t tn2, uintptr_t fn2) {
+    if (!handle || k < 0) return -103;
+    OnepassPlan* p = (OnepassPlan*)handle;
+    if (k == 0) {
+        p->topk = 0; p->scratch2 = nullptr; p->tp2 = p->fp2 = p->tn2 = p->fn2 = nullptr;
+        return 0;
+    }
+    if (!scratch2 || !tp2 || !fp2 || !tn2 || !fn2) return -103;
+    p->topk = k; p->scratch2 = (ull*)scratch2;
+    p->tp2 = (ll*)tp2; p->fp2 = (ll*)fp2; p->tn2 = (ll*)tn2; p->fn2 = (ll*)fn2;
     return 0;
 }
 

@@ -257,6 +257,68 @@ __device__ __forceinline__ bool count_row(long long t, long long p, long long C,
     return true;
 }
 
+// ---- top-k slot: rank of the target's logit, and the row's second count ----
+// rank = #{ j : x[j] > x[t] or (x[j] == x[t] and j < t) }, IEEE compares: a
+// NaN element never counts, a NaN x[t] has rank 0, +0.0 and -0.0 tie and the
+// index decides. The effective prediction of the slot is t if rank < k, else
+// the argmax p (the reference's _refine_preds_oh). c = index of f[0].
+template <int K, typename Idx>
+__device__ __forceinline__ void rank_fold(const float (&f)[K], Idx c, float xt, Idx t,
+                                          unsigned int& cnt) {
+#pragma unroll
+    for (int i = 0; i < K; i++) cnt += (f[i] > xt || (f[i] == xt && c + i < t)) ? 1u : 0u;
+}
+
+// element e of a row held in registers (r[k] is vector lane + 64*k of the
+// row), returned to every lane: the 32-bit word is picked out of the lane's
+// registers and read from the lane that holds it. e must be wave-uniform and
+// inside the row. No memory access.
+template <typename T, int NV>
+__device__ __forceinline__ float row_element(const uint4 (&r)[NV], int e) {
+    constexpr int EPV = 16 / sizeof(T);
+    const int vec = e / EPV, i = e % EPV;
+    const int wi = (vec >> 6) * 4 + (is_bf16_v<T> ? (i >> 1) : i);  // word of the lane's slice
+    unsigned int w = r[0].x;
+#pragma unroll
+    for (int q = 1; q < 4 * NV; q++) {
+        const unsigned int cand = (q & 3) == 0 ? r[q >> 2].x
+                                : (q & 3) == 1 ? r[q >> 2].y
+                                : (q & 3) == 2 ? r[q >> 2].z
+                                               : r[q >> 2].w;
+        w = (wi == q) ? cand : w;
+    }
+    w = (unsigned int)__builtin_amdgcn_readlane((int)w, vec & 63);
+    if constexpr (is_bf16_v<T>) return __uint_as_float((i & 1) ? (w & 0xffff0000u) : (w << 16));
+    else return __uint_as_float(w);
+}
+
+// sum over the 64 lanes, lane l with lane l + off for off = 32 ... 1; the sum
+// lands in lane 0. All 64 lanes must be active.
+__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int x) {
+    x += lane_down_u32<32>(x);
+    x += lane_down_u32<16>(x);
+    x += lane_down_u32<8>(x);
+    x += lane_down_u32<4>(x);
+    x += lane_down_u32<2>(x);
+    x += lane_down_u32<1>(x);
+    return x;
+}
+
+// Called next to count_row, for a row count_row accepted (so t and p are in
+// range): the slot shares the top-1 `valid`.
+__device__ __forceinline__ void count_row_topk(long long t, long long p, unsigned int rank, int k,
+                                               unsigned long long* __restrict__ tp,
+                                               unsigned long long* __restrict__ fp,
+                                               unsigned long long* __restrict__ fn) {
+    const long long pk = rank < (unsigned int)k ? t : p;
+    if (pk == t) {
+        atomicAdd(&tp[t], 1ULL);
+    } else {
+        atomicAdd(&fp[pk], 1ULL);
+        atomicAdd(&fn[t], 1ULL);
+    }
+}
+
 // ---- "some element of the batch lies outside [0,1]" ----
 // wave OR of the per-thread bit, then one LDS OR per wave that saw it; the
 // caller zeroes *blk_outside before and syncs the block after

@@ -48,6 +48,8 @@ _D = ctypes.c_double
 
 _SIGNATURES = {
     "ma_mc_stat_logits": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
+    "ma_mc_stat_logits_topk": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _U64, _U64, _U64],
+    "ma_mc_stat_topk_covers": [_LL],
     "ma_mc_stat_labels": [_U64, _U64, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64],
     "ma_bincount": [_U64, _U64, _LL, _LL, _U64],
     "ma_binary_stat": [_U64, _U64, _I, _U64, _LL, _F, _LL, _I, _U64, _U64],
@@ -68,7 +70,10 @@ _SIGNATURES = {
     "ma_mc_onepass_update": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64],
     "ma_onepass_plan_create": [_I, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64, ctypes.POINTER(ctypes.c_ulonglong)],
     "ma_onepass_plan_step": [_U64, _U64, _U64, _U64, _LL],
+    "ma_onepass_plan_set_topk": [_U64, _I, _U64, _U64, _U64, _U64, _U64],
     "ma_apply_stat_exact": [_U64, _U64, _LL, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
+    "ma_apply_stat_exact_topk": [_U64, _U64, _LL, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
+    "ma_apply_stat_deltas_topk": [_U64, _U64, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
     "ma_curve_auc_from_confmat": [_U64, _U64, _I, _LL, _I, _U64, _U64],
     "ma_err_reduce": [_U64, _U64, _U64, _I, _LL, _I, _D, _U64, _I, _I, _U64],
     "ma_box_iou": [_U64, _U64, _LL, _U64, _LL, _I, _U64],
@@ -149,14 +154,16 @@ def _to_supported(t: Tensor) -> Tensor:
 def _launch_mc_stat(
     preds: Tensor, target: Tensor, C: int, ignore_index: Optional[int],
     tp_ptr: int, fp_ptr: int, fn_ptr: int, confmat_ptr: int, valid_ptr: int,
-    argmax_ptr: int = 0, rowstats=None,
+    argmax_ptr: int = 0, rowstats=None, topk=None,
 ) -> int:
     """The one stat launch every multiclass update shares: ``ma_mc_stat_logits``
     for (B, C) float ``preds`` (fused row-argmax), ``ma_mc_stat_labels`` for
     integer label ``preds``. Counts land in the (C,) u64 buffers behind the
     pointers (``confmat_ptr``/``argmax_ptr`` may be 0); ``rowstats`` =
     (rowmax, rowinv, epoch_buf) also emits the softmax row statistics (logits
-    only). Returns B, the number of samples."""
+    only). ``topk`` = (k, scratch2) adds the top-k slot (logits only, C the
+    slot covers): its counts land in the (3*C,) ``scratch2``. Returns B, the
+    number of samples."""
     lib = _lib()
     ign = (ignore_index if ignore_index is not None else 0, 1 if ignore_index is not None else 0)
     if preds.ndim == 2 and preds.is_floating_point():
@@ -165,6 +172,16 @@ def _launch_mc_stat(
         B = preds.shape[0]
         assert preds.shape[1] == C, "preds must be (B, num_classes)"
         rs = [t.data_ptr() for t in rowstats] if rowstats is not None else [0, 0, 0]
+        if topk is not None:
+            k, scratch2 = topk
+            p2 = scratch2.data_ptr()
+            rc = lib.ma_mc_stat_logits_topk(
+                _stream(), preds.data_ptr(), _dtype_code(preds), target.data_ptr(), B, C, *ign,
+                tp_ptr, fp_ptr, fn_ptr, confmat_ptr, valid_ptr, argmax_ptr, *rs,
+                k, p2, p2 + 8 * C, p2 + 16 * C,
+            )
+            _check(rc, "ma_mc_stat_logits_topk")
+            return B
         rc = lib.ma_mc_stat_logits(
             _stream(), preds.data_ptr(), _dtype_code(preds), target.data_ptr(), B, C, *ign,
             tp_ptr, fp_ptr, fn_ptr, confmat_ptr, valid_ptr, argmax_ptr, *rs,
@@ -182,11 +199,12 @@ def _launch_mc_stat(
     return B
 
 
-def _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch: Tensor, confmat_ptr=0, rowstats=None) -> int:
+def _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch: Tensor, confmat_ptr=0, rowstats=None,
+                            topk=None) -> int:
     """:func:`_launch_mc_stat` into a (3*C+1,) int64 scratch laid out [tp|fp|fn|valid]."""
     p = scratch.data_ptr()
     return _launch_mc_stat(preds, target, C, ignore_index, p, p + 8 * C, p + 16 * C, confmat_ptr,
-                           p + 24 * C, rowstats=rowstats)
+                           p + 24 * C, rowstats=rowstats, topk=topk)
 
 
 def _fresh_mc_stat(preds, target, C, ignore_index, want_confmat, argmax: Optional[Tensor] = None):
@@ -1232,13 +1250,39 @@ def curve_auc_from_confmat(confmat_state: Tensor, mode: int) -> Tuple[Tensor, Te
     return out, weights
 
 
+# Top-k slot of the fused collection step. METRICS_AMD_FUSE_TOPK=0 keeps every
+# top-k stat leader out of the fused plan: it then updates on its own through
+# mc_topk_stat, exactly as before (A/B lever and escape hatch). Read when a
+# collection builds its fused plan.
+FUSE_TOPK_ENV = "METRICS_AMD_FUSE_TOPK"
+_TOPK_COVERS_CACHE: dict = {}
+
+
+def fuse_topk_enabled() -> bool:
+    return os.environ.get(FUSE_TOPK_ENV, "1") != "0"
+
+
+def mc_stat_topk_covers(num_classes: int) -> bool:
+    """Whether the streaming stat kernel has the top-k slot at this class count
+    (the thread-per-row kernel for small C has none)."""
+    hit = _TOPK_COVERS_CACHE.get(num_classes)
+    if hit is None:
+        hit = _TOPK_COVERS_CACHE[num_classes] = bool(_lib().ma_mc_stat_topk_covers(num_classes))
+    return hit
+
+
 def mc_fused_collection_update(
     preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int],
     stat=None, confmat=None, exact=None, rowstats=None, defer_apply: bool = False,
-    bump_epoch_ptr: int = 0,
+    bump_epoch_ptr: int = 0, topk=None,
 ):
     """Collection-level fused update: ONE pass over the (B, C) logits feeds the
     stat-scores, confusion-matrix and exact-match leaders at once.
+
+    ``topk`` = (k, scratch2, tp, fp, tn, fn) — the top-k stat leader's slot:
+    the same pass counts its effective prediction into the (3*C,) ``scratch2``
+    and the same apply launch adds it to its states. Logits only, and only
+    where :func:`mc_stat_topk_covers` says so (the caller checks).
 
     ``stat``  = (scratch, tp, fp, tn, fn) — required (owns the count scratch)
     ``confmat`` = confmat state tensor (atomics accumulate directly) or None
@@ -1254,6 +1298,7 @@ def mc_fused_collection_update(
     B = _launch_mc_stat_scratch(
         preds, target, C, ignore_index, scratch,
         confmat.data_ptr() if confmat is not None else 0, rowstats,
+        topk=topk[:2] if topk is not None else None,
     )
 
     def _apply_pass() -> None:
@@ -1261,7 +1306,17 @@ def mc_fused_collection_update(
         # the lazy curve hist rides the same stream the caller defers this so
         # it lands AFTER the hist kernel and closes the device epoch for free
         # (a separate 1-thread bump kernel costs a full ~4us dispatch)
-        if exact is not None:
+        if topk is not None:
+            correct, total = exact if exact is not None else (None, None)
+            rc2 = lib.ma_apply_stat_exact_topk(
+                _stream(), scratch.data_ptr(), C, B if exact is not None else 0,
+                tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(),
+                correct.data_ptr() if correct is not None else 0,
+                total.data_ptr() if total is not None else 0, bump_epoch_ptr,
+                *(t.data_ptr() for t in topk[1:]),
+            )
+            _check(rc2, "ma_apply_stat_exact_topk")
+        elif exact is not None:
             correct, total = exact
             rc2 = lib.ma_apply_stat_exact(
                 _stream(), scratch.data_ptr(), C, B,
@@ -1279,6 +1334,8 @@ def mc_fused_collection_update(
     if confmat is not None:
         _mark_kernel_mutated(confmat)
     _mark_kernel_mutated(tp)  # generation key for the batched linear-stat plan
+    if topk is not None:
+        _mark_kernel_mutated(topk[2])  # the top-k group's own linear-stat plan
     if defer_apply:
         return _apply_pass
     _apply_pass()
@@ -1312,8 +1369,9 @@ class _OnepassPlan:
     __slots__ = ("handle", "tensors", "scalars", "thr", "_destroy")
 
     def __init__(self, lib, tensors, scalars, thr: Tensor):
-        scratch, tp, fp, tn, fn, confmat, correct, total, rowstats_buf, epoch_buf, hist, cs, _ = tensors
-        dt, C, T, ignore_index = scalars
+        (scratch, tp, fp, tn, fn, confmat, correct, total, rowstats_buf, epoch_buf, hist, cs,
+         scratch2, tp2, fp2, tn2, fn2, _) = tensors
+        dt, C, T, ignore_index, k = scalars
         uni, t0, inv_step = _uniform_params(thr)
         rs_ptr = rowstats_buf.data_ptr()
         handle = ctypes.c_ulonglong(0)
@@ -1335,6 +1393,12 @@ class _OnepassPlan:
         self.scalars = scalars
         self.thr = thr
         self._destroy = lib.ma_onepass_plan_destroy
+        if k:  # the top-k slot
+            rc = lib.ma_onepass_plan_set_topk(
+                self.handle, k, scratch2.data_ptr(), tp2.data_ptr(), fp2.data_ptr(),
+                tn2.data_ptr(), fn2.data_ptr(),
+            )
+            _check(rc, "ma_onepass_plan_set_topk")
 
     def __del__(self):
         if self.handle:
@@ -1351,7 +1415,7 @@ class _OnepassPlan:
 def mc_onepass_update(
     preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int],
     stat, confmat: Optional[Tensor], exact, rowstats_buf: Tensor, epoch_buf: Tensor, curve,
-    force: bool = False,
+    force: bool = False, topk=None,
 ) -> bool:
     """The whole fused-collection step (stat scores, confusion matrix, exact
     match, threshold-curve histogram) in ONE native call that reads the logits
@@ -1366,6 +1430,8 @@ def mc_onepass_update(
     ``stat``/``exact`` as in :func:`mc_fused_collection_update`;
     ``rowstats_buf`` is the (2, >=B) float32 rowmax/rowinv buffer, ``epoch_buf``
     the curve leader's device-epoch buffer, ``curve`` the curve leader (owns the histogram and the curve scratch).
+    ``topk`` = (k, scratch2, tp, fp, tn, fn): the top-k stat leader's slot, as
+    in :func:`mc_fused_collection_update`; every shape the kernel covers has it.
     """
     lib = _lib()
     C = num_classes
@@ -1408,9 +1474,10 @@ def mc_onepass_update(
     tensors = (
         scratch, tp, fp, tn, fn, confmat,
         exact[0] if exact is not None else None, exact[1] if exact is not None else None,
-        rowstats_buf, epoch_buf, hist, cs, thr_src,
+        rowstats_buf, epoch_buf, hist, cs,
+        *(topk[1:] if topk is not None else (None,) * 5), thr_src,
     )
-    scalars = (dt, C, T, ignore_index)
+    scalars = (dt, C, T, ignore_index, topk[0] if topk is not None else 0)
     if plan is None or plan.scalars != scalars or not all(map(operator.is_, plan.tensors, tensors)):
         plan = curve.__dict__["_hip_onepass_plan"] = _OnepassPlan(lib, tensors, scalars, thr)
     rc = lib.ma_onepass_plan_step(plan.handle, _stream(), preds.data_ptr(), target.data_ptr(), preds.shape[0])
@@ -1418,6 +1485,8 @@ def mc_onepass_update(
     if confmat is not None:
         _mark_kernel_mutated(confmat)
     _mark_kernel_mutated(tp)
+    if topk is not None:
+        _mark_kernel_mutated(topk[2])
     # same lazy protocol as curve_hist_into_confmat: the histogram accumulates,
     # the suffix/confmat materialization waits for the first state read
     curve.__dict__["_hip_lazy_meta"] = (C, T, 1)
