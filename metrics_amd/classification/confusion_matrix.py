@@ -87,17 +87,12 @@ def _fused_confmat_update(metric, preds, target) -> bool:
     Returns False when the caller must take the torch path."""
     if not (preds.is_cuda and (not preds.is_floating_point() or preds.dtype in (torch.float32, torch.bfloat16))):
         return False
-    if preds.ndim == target.ndim + 1 and preds.is_floating_point():
-        p2 = preds.reshape(preds.shape[0], preds.shape[1], -1).movedim(1, -1).reshape(-1, preds.shape[1])
-    else:
-        p2 = preds.reshape(-1)
     from metrics_amd.ops import _hip
 
-    dummy = getattr(metric, "_hip_dummy", None)
-    if dummy is None or dummy.device != preds.device:
-        dummy = torch.zeros(3 * metric.num_classes + 1, dtype=torch.long, device=preds.device)
-        metric._hip_dummy = dummy
-    _hip.mc_confmat_into(p2, target.reshape(-1), metric.num_classes, metric.ignore_index, metric.confmat, dummy)
+    _hip.mc_confmat_into(
+        *_hip.rows_by_class(preds, target), metric.num_classes, metric.ignore_index, metric.confmat,
+        _hip.mc_count_block(metric, metric.num_classes, preds.device, key="_hip_dummy"),
+    )
     return True
 
 

@@ -79,10 +79,7 @@ class MulticlassExactMatch(Metric):
             # stat kernel, correct = sum(tp), total = valid (2 launches)
             from metrics_amd.ops import _hip
 
-            scratch = getattr(self, "_hip_scratch", None)
-            if scratch is None or scratch.device != preds.device:
-                scratch = torch.zeros(3 * self.num_classes + 1, dtype=torch.long, device=preds.device)
-                self._hip_scratch = scratch
+            scratch = _hip.mc_count_block(self, self.num_classes, preds.device)
             _hip.mc_exact_into(preds, target, self.num_classes, self.ignore_index, scratch, self.correct, self.total)
             return
         preds, target = _multiclass_stat_scores_format(preds, target, 1)

@@ -199,16 +199,9 @@ class MulticlassStatScores(_AbstractStatScores):
         ):
             from metrics_amd.ops import _hip
 
-            if preds.ndim == target.ndim + 1 and preds.is_floating_point():
-                p2 = preds.reshape(preds.shape[0], preds.shape[1], -1).movedim(1, -1).reshape(-1, preds.shape[1])
-            else:
-                p2 = preds.reshape(-1)
-            scratch = getattr(self, "_hip_scratch", None)
-            if scratch is None or scratch.device != preds.device:
-                scratch = torch.zeros(3 * self.num_classes + 1, dtype=torch.long, device=preds.device)
-                self._hip_scratch = scratch
             _hip.mc_stat_into(
-                p2, target.reshape(-1), self.num_classes, self.ignore_index, scratch,
+                *_hip.rows_by_class(preds, target), self.num_classes, self.ignore_index,
+                _hip.mc_count_block(self, self.num_classes, preds.device),
                 self.tp, self.fp, self.tn, self.fn,
             )
             return

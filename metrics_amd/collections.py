@@ -17,7 +17,7 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from copy import deepcopy
-from typing import Any, Dict, Hashable, Iterable, Iterator, List, Mapping, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, Hashable, Iterable, Iterator, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -36,6 +36,22 @@ def _strip_prefix(s: str, prefix: str) -> str:
 
 def _strip_suffix(s: str, suffix: str) -> str:
     return s[: -len(suffix)] if s.endswith(suffix) else s
+
+
+class _StepBuffers(NamedTuple):
+    """The per-step buffers of the fused update and what they were made for
+    (``_FusedMulticlassUpdatePlan._step_buffers``); None without their leader."""
+
+    device: Any
+    rows: int  # capacity of rowstats
+    logits: bool
+    counts: Tensor
+    topk_counts: Optional[Tensor]
+    rowstats: Optional[Tensor]
+    epoch_buf: Optional[Tensor]
+
+
+_NO_OWNER: dict = {}  # the __dict__ of a leader that takes no part: holds no buffer
 
 
 class _FusedMulticlassUpdatePlan:
@@ -66,6 +82,41 @@ class _FusedMulticlassUpdatePlan:
         self.onepass = curve is not None and mode != 0
         self.onepass_force = mode == 2
         self.onepass_steps = 0
+        self._kept: Optional[_StepBuffers] = None
+
+    def _step_buffers(self, _hip, dev, rows: int, logits: bool) -> "_StepBuffers":
+        """The buffers of a step of ``rows`` rows on ``dev``. Each lives in its
+        leader's ``__dict__`` (:func:`owner_buffer`). The record of the last
+        step is kept and serves again while device, row capacity and kind of
+        predictions fit and every buffer still IS the one its owner holds, the
+        same identity rule as ``_NativePlan.fits``; that costs a fraction of
+        looking each buffer up again. Label predictions take neither the curve
+        leader nor the top-k slot along, so they get none of their buffers."""
+        stat, curve, topk = self.stat, self.curve, self.topk
+        C = stat.num_classes
+        if not logits:
+            curve = topk = None
+        elif topk is not None and not _hip.mc_stat_topk_covers(C):
+            topk = None
+        kept = self._kept
+        curve_own = curve.__dict__ if curve is not None else _NO_OWNER
+        if (
+            kept is not None and kept.device == dev and rows <= kept.rows and kept.logits == logits
+            and kept.counts is stat.__dict__.get("_hip_scratch")
+            and kept.topk_counts is (topk.__dict__ if topk is not None else _NO_OWNER).get("_hip_scratch")
+            and kept.rowstats is curve_own.get("_hip_rowstats_buf")
+            and kept.epoch_buf is curve_own.get("_hip_epoch_buf")
+        ):
+            return kept
+        rowstats = _hip._rowstats_buf(curve, rows, dev) if curve is not None else None
+        kept = self._kept = _StepBuffers(
+            device=dev, rows=rowstats.shape[1] if rowstats is not None else rows, logits=logits,
+            counts=_hip.mc_count_block(stat, C, dev),
+            topk_counts=_hip.mc_count_block(topk, C, dev, valid=False) if topk is not None else None,
+            rowstats=rowstats,
+            epoch_buf=_hip._epoch_buf(dev, curve) if curve is not None else None,
+        )
+        return kept
 
     @staticmethod
     def build(collection) -> "Optional[_FusedMulticlassUpdatePlan]":
@@ -133,72 +184,50 @@ class _FusedMulticlassUpdatePlan:
 
         if not _hip.hip_available():
             return ()
-        stat = self.stat
-        scratch = getattr(stat, "_hip_scratch", None)
-        if scratch is None or scratch.device != preds.device:
-            scratch = torch.zeros(3 * stat.num_classes + 1, dtype=torch.long, device=preds.device)
-            stat._hip_scratch = scratch
+        stat, confmat, exact, curve, topk = self.stat, self.confmat, self.exact, self.curve, self.topk
+        C, dev = stat.num_classes, preds.device
         # the top-k slot rides a step over float logits at a class count the
-        # stat kernel's slot covers (the one-pass kernel covers no smaller one)
-        topk = self.topk
-        slot = None
-        if topk is not None and preds.is_floating_point() and _hip.mc_stat_topk_covers(stat.num_classes):
-            scratch2 = getattr(topk, "_hip_scratch", None)
-            if scratch2 is None or scratch2.device != preds.device:
-                scratch2 = torch.zeros(3 * stat.num_classes, dtype=torch.long, device=preds.device)
-                topk._hip_scratch = scratch2
-            slot = (topk.top_k, scratch2, topk.tp, topk.fp, topk.tn, topk.fn)
-        else:
+        # stat kernel's slot covers (the one-pass kernel covers no smaller one);
+        # label preds: the curve leader can't ride the fused pass either
+        bufs = self._step_buffers(_hip, dev, preds.shape[0], preds.is_floating_point())
+        if bufs.epoch_buf is None:
+            curve = None
+        if bufs.topk_counts is None:
             topk = None
-        curve = self.curve
-        rowstats = None
-        if curve is not None and preds.is_floating_point():
-            # the fused pass also emits softmax row-stats + the epoch flag;
-            # the curve leader's own row-stats kernel is skipped
-            rbuf = curve.__dict__.get("_hip_rowstats_buf")
-            if rbuf is None or rbuf.device != preds.device or rbuf.shape[1] < preds.shape[0]:
-                rbuf = torch.empty(2, preds.shape[0], dtype=torch.float32, device=preds.device)
-                curve.__dict__["_hip_rowstats_buf"] = rbuf
-            ebuf = _hip._epoch_buf(preds.device, curve)
-            # one native call for the whole step, logits read once; False ->
-            # shape not covered, nothing launched, keep the kernel sequence below
-            if self.onepass and _hip.mc_onepass_update(
-                preds, target, stat.num_classes, stat.ignore_index,
-                (scratch, stat.tp, stat.fp, stat.tn, stat.fn),
-                self.confmat.confmat if self.confmat is not None else None,
-                (self.exact.correct, self.exact.total) if self.exact is not None else None,
-                rbuf, ebuf, curve, self.onepass_force, slot,
-            ):
-                self.onepass_steps += 1
-                if topk is not None:
-                    self.topk_steps += 1
-                    return (*self.leaders, topk)
-                return self.leaders
-            rowstats = (rbuf[0], rbuf[1], ebuf)
-        elif curve is not None:
-            curve = None  # label preds: curve can't ride the fused pass
-        deferred = _hip.mc_fused_collection_update(
-            preds, target, stat.num_classes, stat.ignore_index,
-            stat=(scratch, stat.tp, stat.fp, stat.tn, stat.fn),
-            confmat=self.confmat.confmat if self.confmat is not None else None,
-            exact=(self.exact.correct, self.exact.total) if self.exact is not None else None,
-            rowstats=rowstats,
-            # the curve hist must read the epoch flag BEFORE it closes: defer
-            # the apply launch behind the hist so its single block closes the
-            # epoch for free (saves a dedicated ~4us bump dispatch per step)
-            defer_apply=curve is not None,
-            bump_epoch_ptr=rowstats[2].data_ptr() if curve is not None else 0,
-            topk=slot,
+        # the participants of this step, by name: either path below gets them.
+        # With a curve leader the pass also emits softmax row-stats + the epoch
+        # flag, and the leader's own row-stats kernel is skipped.
+        step = _hip.McStepTensors(
+            counts=bufs.counts,
+            confmat=confmat.confmat if confmat is not None else None,
+            tp=stat.tp, fp=stat.fp, tn=stat.tn, fn=stat.fn,
+            correct=exact.correct if exact is not None else None,
+            total=exact.total if exact is not None else None,
+            rowstats=bufs.rowstats, epoch_buf=bufs.epoch_buf,
         )
-        if curve is not None:
-            _hip.curve_hist_into_confmat(
-                preds, target, curve.thresholds, curve.ignore_index, curve.confmat,
-                mode=0, norm="softmax", owner=curve, stats_ready=True, skip_epoch_bump=True,
-            )
-            deferred()
-            handled = self.leaders
+        if topk is not None:
+            step = step._replace(topk_counts=bufs.topk_counts, tp_k=topk.tp, fp_k=topk.fp, tn_k=topk.tn, fn_k=topk.fn)
+        k = topk.top_k if topk is not None else 0
+        # one native call for the whole step, logits read once; False -> shape
+        # not covered, nothing launched, keep the three launches below
+        if curve is not None and self.onepass and _hip.mc_onepass_update(
+            preds, target, C, stat.ignore_index, step, k, curve, self.onepass_force
+        ):
+            self.onepass_steps += 1
         else:
-            handled = tuple(m for m in self.leaders if m is not self.curve)
+            rec = _hip.mc_step(C, stat.ignore_index, step, k)
+            B = _hip.mc_step_count(rec, preds, target)
+            if curve is not None:
+                _hip.curve_hist_into_confmat(
+                    preds, target, curve.thresholds, curve.ignore_index, curve.confmat,
+                    mode=0, norm="softmax", owner=curve, stats_ready=True, skip_epoch_bump=True,
+                )
+            # the curve hist reads the epoch flag BEFORE it closes: the apply
+            # launch goes behind the hist and its single block closes the epoch
+            # for free (saves a dedicated ~4us bump dispatch per step)
+            _hip.mc_step_apply(rec, B, close_epoch=curve is not None)
+            _hip.mc_step_mark_mutated(step)
+        handled = self.leaders if curve is not None else tuple(m for m in self.leaders if m is not self.curve)
         if topk is not None:
             self.topk_steps += 1
             handled = (*handled, topk)
@@ -220,7 +249,6 @@ class _FusedMulticlassComputePlan:
         "exact": ("correct", "total"),
         "curve_auc": ("confmat",),
     }
-    _KINDS = tuple(_STATES)
 
     def __init__(self, leaders, members):
         # kind -> leader metric; (metric, kind, spec, slot) per covered member:
@@ -262,39 +290,41 @@ class _FusedMulticlassComputePlan:
             members.append((m, kind, spec, slot))
         return cls(leaders, members)
 
-    def _state_tensors(self):
-        """The leaders' state tensors in the native plan's order, or None if a
-        state is not a tensor (list states) or the shapes do not fit one plan."""
-        out = []
-        for kind in self._KINDS:
-            leader = self.leaders.get(kind)
+    def _state_tensors(self, _hip):
+        """The leaders' state tensors as the native plan's ``ComputeStates``, or
+        None if a state is not a tensor (list states)."""
+        out = {}
+        for kind, leader in self.leaders.items():
             for name in self._STATES[kind]:
-                t = getattr(leader, name) if leader is not None else None
-                if leader is not None and not isinstance(t, Tensor):
+                t = getattr(leader, name)
+                if not isinstance(t, Tensor):
                     return None
-                out.append(t)
+                # both the confusion-matrix and the curve group call their state "confmat"
+                out["curve_state" if kind == "curve_auc" else name] = t
         curve = self.leaders.get("curve_auc")
-        out.append(curve.__dict__.get("_hip_hist_buf") if curve is not None else None)
-        return tuple(out)
+        if curve is not None:
+            out["hist"] = curve.__dict__.get("_hip_hist_buf")
+        return _hip.ComputeStates(**out)
 
-    def _build_native(self, tensors):
+    def _build_native(self, states):
+        """A native plan over ``states``, or None if they do not fit one plan."""
         from metrics_amd.ops import _hip
 
-        tp, fp, tn, fn, confmat, correct, total, curve_state, hist = tensors
-        present = [t for t in tensors if t is not None]
+        tp, confmat, curve_state, hist = states.tp, states.confmat, states.curve_state, states.hist
+        present = [t for t in states if t is not None]
         dev = present[0].device
         if not all(t.is_cuda and t.device == dev and t.is_contiguous() and t.dtype == torch.long for t in present):
             return None
         sizes = set()
         if tp is not None:
-            if tp.ndim != 1 or not (tp.shape == fp.shape == tn.shape == fn.shape):
+            if tp.ndim != 1 or not (tp.shape == states.fp.shape == states.tn.shape == states.fn.shape):
                 return None
             sizes.add(tp.numel())
         if confmat is not None:
             if confmat.ndim != 2 or confmat.shape[0] != confmat.shape[1]:
                 return None
             sizes.add(confmat.shape[0])
-        if correct is not None and (correct.numel() != 1 or total.numel() != 1):
+        if states.correct is not None and (states.correct.numel() != 1 or states.total.numel() != 1):
             return None
         T = 1
         if curve_state is not None:
@@ -307,11 +337,7 @@ class _FusedMulticlassComputePlan:
         if len(sizes) > 1:
             return None
         C = sizes.pop() if sizes else 1
-        return _hip._ComputePlan(
-            dev, C, T, (tp, fp, tn, fn) if tp is not None else None, confmat,
-            (correct, total) if correct is not None else None,
-            (hist, curve_state) if curve_state is not None else None, self.formulas, 0.0,
-        )
+        return _hip._ComputePlan(dev, C, T, states, self.formulas, 0.0)
 
     def try_run(self) -> bool:
         """Fill ``_computed`` of every covered member that has no cached result.
@@ -321,7 +347,7 @@ class _FusedMulticlassComputePlan:
 
         if not (_hip.compute_plan_enabled() and _hip.hip_available()) or tracing.is_enabled():
             return False
-        tensors = self._state_tensors()
+        tensors = self._state_tensors(_hip)
         if tensors is None:
             return False
         todo = []
@@ -355,8 +381,8 @@ class _FusedMulticlassComputePlan:
         curve = self.leaders.get("curve_auc")
         flush = False
         if curve is not None and curve.__dict__.get("_lazy_dirty"):
-            C, T = tensors[7].shape[1], tensors[7].shape[0]
-            if curve.__dict__.get("_hip_lazy_meta") != (C, T, 1) or tensors[8] is None:
+            T, C = tensors.curve_state.shape[:2]
+            if curve.__dict__.get("_hip_lazy_meta") != (C, T, 1) or tensors.hist is None:
                 return False
             curve.__dict__["_lazy_dirty"] = False  # the step is the flush
             flush = True

@@ -29,6 +29,7 @@
 
 #include "compute_common.h"
 #include "curve_common.h"
+#include "mc_step.h"
 
 #define WAVE 64
 #define CHECK(x)                                                                                   \
@@ -780,16 +781,14 @@ __global__ void k_epoch_bump(unsigned int* __restrict__ E) {
 // exact-match epilogue: correct += sum(tp), total += valid — one block,
 // zeroes the scratch in-flight (same valid-slot protocol as k_apply_stat_exact).
 __global__ void k_exact_apply(unsigned long long* __restrict__ scratch, ll C, ll B,
-                              int zero_scratch, ll* __restrict__ correct, ll* __restrict__ total) {
+                              ll* __restrict__ correct, ll* __restrict__ total) {
     __shared__ unsigned long long part[256];
     unsigned long long acc = 0;
     for (ll i = threadIdx.x; i < C; i += blockDim.x) {
         acc += scratch[i];
-        if (zero_scratch) {
-            scratch[i] = 0;
-            scratch[C + i] = 0;
-            scratch[2 * C + i] = 0;
-        }
+        scratch[i] = 0;
+        scratch[C + i] = 0;
+        scratch[2 * C + i] = 0;
     }
     part[threadIdx.x] = acc;
     __syncthreads();
@@ -803,7 +802,7 @@ __global__ void k_exact_apply(unsigned long long* __restrict__ scratch, ll C, ll
         const ll valid = (ll)scratch[3 * C];
         correct[0] += (ll)part[0] + (B - valid);
         total[0] += B;
-        if (zero_scratch) scratch[3 * C] = 0;
+        scratch[3 * C] = 0;
     }
 }
 
@@ -1026,78 +1025,115 @@ static int mc_stat_smallc() {
 
 extern "C" {
 
-// whether ma_mc_stat_logits_topk covers C classes: the thread-per-row kernel
-// for small C has no top-k slot
+// whether ma_mc_stat_logits has the top-k slot at C classes: the thread-per-row
+// kernel for small C has none
 int ma_mc_stat_topk_covers(ll C) { return C > mc_stat_smallc() ? 1 : 0; }
 
-// ma_mc_stat_logits with the top-k slot: also counts, per valid row, the
-// effective prediction "target if it ranks inside the top k, else the argmax"
-// into tp2/fp2/fn2 ((C,) u64 each). -103 where the slot is not covered.
-int ma_mc_stat_logits_topk(uintptr_t stream, uintptr_t preds, int dtype /*0=f32 1=bf16*/,
-                           uintptr_t target, ll B, ll C, ll ignore_index, int has_ignore,
-                           uintptr_t tp, uintptr_t fp, uintptr_t fn, uintptr_t confmat,
-                           uintptr_t valid_count, uintptr_t argmax_out, uintptr_t rowmax,
-                           uintptr_t rowinv, uintptr_t epoch_buf, int k, uintptr_t tp2,
-                           uintptr_t fp2, uintptr_t fn2) {
-    typedef unsigned long long ull;
+// Count pass over (B, C) logits into the record's count block (and confmat,
+// row statistics, argmax_out where given). The top-k slot is on iff st->k > 0:
+// the pass then also counts, per valid row, the effective prediction "target if
+// it ranks inside the top k, else the argmax" into topk_counts. -103 where the
+// slot is asked for but not covered, or a buffer it needs is missing.
+int ma_mc_stat_logits(uintptr_t stream, const McStep* st, uintptr_t preds,
+                      int dtype /*0=f32 1=bf16*/, uintptr_t target, ll B, uintptr_t argmax_out) {
     hipStream_t s = (hipStream_t)stream;
-    if (!ma_mc_stat_topk_covers(C) || k < 1 || !tp2 || !fp2 || !fn2) return -103;
-    const int grid = grid_for(B, mc_stat_rows_div());
-    if (dtype == 0)
-        k_mc_stat_logits<float, true><<<grid, 256, 0, s>>>(
-            (const float*)preds, (const ll*)target, B, C, ignore_index, has_ignore, (ull*)tp,
-            (ull*)fp, (ull*)fn, (ull*)confmat, (ull*)valid_count, (ll*)argmax_out, (float*)rowmax,
-            (float*)rowinv, (unsigned int*)epoch_buf, k, (ull*)tp2, (ull*)fp2, (ull*)fn2);
-    else
-        k_mc_stat_logits<unsigned short, true><<<grid, 256, 0, s>>>(
-            (const unsigned short*)preds, (const ll*)target, B, C, ignore_index, has_ignore,
-            (ull*)tp, (ull*)fp, (ull*)fn, (ull*)confmat, (ull*)valid_count, (ll*)argmax_out,
-            (float*)rowmax, (float*)rowinv, (unsigned int*)epoch_buf, k, (ull*)tp2, (ull*)fp2,
-            (ull*)fn2);
-    return (int)hipGetLastError();
-}
-
-int ma_mc_stat_logits(uintptr_t stream, uintptr_t preds, int dtype /*0=f32 1=bf16*/,
-                      uintptr_t target, ll B, ll C, ll ignore_index, int has_ignore, uintptr_t tp,
-                      uintptr_t fp, uintptr_t fn, uintptr_t confmat, uintptr_t valid_count,
-                      uintptr_t argmax_out, uintptr_t rowmax, uintptr_t rowinv, uintptr_t epoch_buf) {
-    hipStream_t s = (hipStream_t)stream;
+    const ll C = st->C;
+    if (!st->counts) return -103;
+    if (st->k != 0 && (st->k < 0 || !ma_mc_stat_topk_covers(C) || !st->topk_counts)) return -103;
 #define MC_STAT_ARGS                                                                               \
-    (const DT*)preds, (const ll*)target, B, C, ignore_index, has_ignore, (unsigned long long*)tp,  \
-        (unsigned long long*)fp, (unsigned long long*)fn, (unsigned long long*)confmat,            \
-        (unsigned long long*)valid_count, (ll*)argmax_out, (float*)rowmax, (float*)rowinv,         \
-        (unsigned int*)epoch_buf
-    // each wave loops several rows: more vector loads in flight per lane
-    // (latency-bound otherwise; sweep tools/curve_sweep.py analogue)
-    const int rows_div = mc_stat_rows_div();
+    (const DT*)preds, (const ll*)target, B, C, st->ignore_index, (int)st->has_ignore, st->counts,  \
+        st->counts + C, st->counts + 2 * C, st->confmat, st->counts + 3 * C, (ll*)argmax_out,      \
+        st->rowmax, st->rowinv, st->epoch_buf
     // small-C: thread-per-row variant (wave-per-row wastes (64-C)/64 lanes)
     if (C <= mc_stat_smallc()) {
         int grid = grid_for(B, 256);
         if (grid > 4096) grid = 4096;
-        const size_t shmem = (size_t)(3 * C + (confmat && C <= 64 ? C * C : 0)) * sizeof(unsigned int);
+        const size_t shmem =
+            (size_t)(3 * C + (st->confmat && C <= 64 ? C * C : 0)) * sizeof(unsigned int);
         LAUNCH_BY_DTYPE(dtype, k_mc_stat_logits_tiny, grid, 256, shmem, s, MC_STAT_ARGS);
         return (int)hipGetLastError();
     }
-    int grid = grid_for(B, rows_div);
-    LAUNCH_BY_DTYPE(dtype, k_mc_stat_logits, grid, 256, 0, s, MC_STAT_ARGS);
+    // each wave loops several rows: more vector loads in flight per lane
+    // (latency-bound otherwise; sweep tools/curve_sweep.py analogue)
+    const int grid = grid_for(B, mc_stat_rows_div());
+    if (st->k > 0) {
+        unsigned long long* c2 = st->topk_counts;
+        FOR_DTYPE(dtype, (k_mc_stat_logits<DT, true><<<grid, 256, 0, s>>>(
+                             MC_STAT_ARGS, (int)st->k, c2, c2 + C, c2 + 2 * C)));
+    } else {
+        FOR_DTYPE(dtype, (k_mc_stat_logits<DT, false><<<grid, 256, 0, s>>>(MC_STAT_ARGS)));
+    }
 #undef MC_STAT_ARGS
     return (int)hipGetLastError();
 }
 
-int ma_mc_stat_labels(uintptr_t stream, uintptr_t preds, uintptr_t target, ll N, ll C,
-                      ll ignore_index, int has_ignore, uintptr_t tp, uintptr_t fp, uintptr_t fn,
-                      uintptr_t confmat, uintptr_t valid_count) {
+// The same counts from integer label predictions. No row statistics, and no
+// top-k slot: -103 where it is asked for, as above.
+int ma_mc_stat_labels(uintptr_t stream, const McStep* st, uintptr_t preds, uintptr_t target,
+                      ll N) {
     hipStream_t s = (hipStream_t)stream;
+    const ll C = st->C;
+    if (!st->counts || st->k != 0) return -103;
     const int use_lds = C <= 128;
-    const int priv_cm = confmat && C <= 64;
+    const int priv_cm = st->confmat && C <= 64;
     const size_t shmem = use_lds ? (size_t)(3 * C + (priv_cm ? C * C : 0)) * sizeof(unsigned int) : 0;
     int grid = grid_for(N, 256);
     if (grid > 4096) grid = 4096;
     k_mc_stat_labels<<<grid, 256, shmem, s>>>(
-        (const ll*)preds, (const ll*)target, N, C, ignore_index, has_ignore,
-        (unsigned long long*)tp, (unsigned long long*)fp, (unsigned long long*)fn,
-        (unsigned long long*)confmat, (unsigned long long*)valid_count, use_lds, priv_cm);
+        (const ll*)preds, (const ll*)target, N, C, st->ignore_index, (int)st->has_ignore,
+        st->counts, st->counts + C, st->counts + 2 * C, st->confmat, st->counts + 3 * C, use_lds,
+        priv_cm);
     return (int)hipGetLastError();
+}
+
+// Apply pass, one single-block launch: consumes and zeroes the count block (and
+// the top-k block) into the stat states, adds the exact-match counts of the B
+// rows where correct/total are given, and closes the curve epoch (E[1] += 1)
+// when close_epoch is set. A record without stat states is the stand-alone
+// exact-match update; one with neither has nothing to consume, and only an
+// epoch asked for is closed.
+int ma_mc_stat_apply(uintptr_t stream, const McStep* st, ll B, int close_epoch) {
+    hipStream_t s = (hipStream_t)stream;
+    unsigned int* E = close_epoch ? st->epoch_buf : nullptr;
+    if (!st->counts || (close_epoch && !E) || !st->correct != !st->total) return -103;
+    if (!st->tp) {
+        if (st->k != 0) return -103;
+        if (st->correct)
+            k_exact_apply<<<1, 256, 0, s>>>(st->counts, st->C, B, st->correct, st->total);
+        if (E) k_epoch_bump<<<1, 1, 0, s>>>(E);
+        return (int)hipGetLastError();
+    }
+    if (!st->fp || !st->tn || !st->fn) return -103;
+    if (st->k > 0) {
+        if (!st->topk_counts || !st->tp_k || !st->fp_k || !st->tn_k || !st->fn_k) return -103;
+        k_apply_stat_exact<true><<<1, 256, 0, s>>>(st->counts, st->C, B, st->tp, st->fp, st->tn,
+                                                   st->fn, st->correct, st->total, E,
+                                                   st->topk_counts, st->tp_k, st->fp_k, st->tn_k,
+                                                   st->fn_k);
+    } else {
+        k_apply_stat_exact<false><<<1, 256, 0, s>>>(st->counts, st->C, B, st->tp, st->fp, st->tn,
+                                                    st->fn, st->correct, st->total, E, nullptr,
+                                                    nullptr, nullptr, nullptr, nullptr);
+    }
+    return (int)hipGetLastError();
+}
+
+// Host only: every field of a record as u64, in declaration order, and the
+// size of the record, for the layout check of the Python mirror. Returns the
+// number of fields written.
+int ma_mc_step_dump(const McStep* st, unsigned long long* out) {
+    int n = 0;
+#define MC_STEP_DUMP(type, name) out[n++] = (unsigned long long)st->name;
+    MC_STEP_FIELDS(MC_STEP_DUMP)
+#undef MC_STEP_DUMP
+    return n;
+}
+int ma_mc_step_sizeof() { return (int)sizeof(McStep); }
+// the field names in declaration order, each followed by a comma
+const char* ma_mc_step_field_names() {
+#define MC_STEP_NAME(type, name) #name ","
+    return MC_STEP_FIELDS(MC_STEP_NAME);
+#undef MC_STEP_NAME
 }
 
 int ma_bincount(uintptr_t stream, uintptr_t x, ll N, ll bins, uintptr_t out) {
@@ -1303,65 +1339,11 @@ int ma_curve_epoch_bump(uintptr_t stream, uintptr_t epoch_buf) {
     return (int)hipGetLastError();
 }
 
-int ma_apply_stat_deltas(uintptr_t stream, uintptr_t scratch, ll C, uintptr_t tp,
-                         uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t epoch_buf) {
-    hipStream_t s = (hipStream_t)stream;
-    k_apply_stat_exact<false><<<1, 256, 0, s>>>((unsigned long long*)scratch, C, 0, (ll*)tp,
-                                                (ll*)fp, (ll*)tn, (ll*)fn, nullptr, nullptr,
-                                                (unsigned int*)epoch_buf, nullptr, nullptr,
-                                                nullptr, nullptr, nullptr);
-    return (int)hipGetLastError();
-}
-
-// ma_apply_stat_exact with the top-k slot: the same single launch also applies
-// scratch2 = [tp_k|fp_k|fn_k] (3*C u64, consumed and zeroed) to tp2/fp2/tn2/fn2
-// with the same valid. correct/total may be 0, as in ma_apply_stat_deltas.
-int ma_apply_stat_exact_topk(uintptr_t stream, uintptr_t scratch, ll C, ll B, uintptr_t tp,
-                             uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t correct,
-                             uintptr_t total, uintptr_t epoch_buf, uintptr_t scratch2,
-                             uintptr_t tp2, uintptr_t fp2, uintptr_t tn2, uintptr_t fn2) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!scratch2 || !tp2 || !fp2 || !tn2 || !fn2) return -103;
-    k_apply_stat_exact<true><<<1, 256, 0, s>>>((unsigned long long*)scratch, C, B, (ll*)tp,
-                                               (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct, (ll*)total,
-                                               (unsigned int*)epoch_buf,
-                                               (unsigned long long*)scratch2, (ll*)tp2, (ll*)fp2,
-                                               (ll*)tn2, (ll*)fn2);
-    return (int)hipGetLastError();
-}
-
-int ma_apply_stat_deltas_topk(uintptr_t stream, uintptr_t scratch, ll C, uintptr_t tp,
-                              uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t epoch_buf,
-                              uintptr_t scratch2, uintptr_t tp2, uintptr_t fp2, uintptr_t tn2,
-                              uintptr_t fn2) {
-    return ma_apply_stat_exact_topk(stream, scratch, C, 0, tp, fp, tn, fn, 0, 0, epoch_buf,
-                                    scratch2, tp2, fp2, tn2, fn2);
-}
-
 int ma_curve_auc_from_confmat(uintptr_t stream, uintptr_t confmat, int T, ll C, int mode,
                                uintptr_t out, uintptr_t weights) {
     hipStream_t s = (hipStream_t)stream;
     k_curve_auc_from_confmat<<<(unsigned)C, 256, 0, s>>>((const ll*)confmat, T, C, mode,
                                                          (float*)out, (float*)weights);
-    return (int)hipGetLastError();
-}
-
-int ma_apply_stat_exact(uintptr_t stream, uintptr_t scratch, ll C, ll B, uintptr_t tp,
-                        uintptr_t fp, uintptr_t tn, uintptr_t fn, uintptr_t correct,
-                        uintptr_t total, uintptr_t epoch_buf) {
-    hipStream_t s = (hipStream_t)stream;
-    k_apply_stat_exact<false><<<1, 256, 0, s>>>((unsigned long long*)scratch, C, B, (ll*)tp,
-                                                (ll*)fp, (ll*)tn, (ll*)fn, (ll*)correct,
-                                                (ll*)total, (unsigned int*)epoch_buf, nullptr,
-                                                nullptr, nullptr, nullptr, nullptr);
-    return (int)hipGetLastError();
-}
-
-int ma_exact_apply(uintptr_t stream, uintptr_t scratch, ll C, ll B, int zero_scratch,
-                   uintptr_t correct, uintptr_t total) {
-    hipStream_t s = (hipStream_t)stream;
-    k_exact_apply<<<1, 256, 0, s>>>((unsigned long long*)scratch, C, B, zero_scratch,
-                                    (ll*)correct, (ll*)total);
     return (int)hipGetLastError();
 }
 
@@ -1381,7 +1363,5 @@ int ma_box_iou(uintptr_t stream, uintptr_t b1, ll N, uintptr_t b2, ll M, int var
     k_box_iou<<<grid, 256, 0, s>>>((const float*)b1, N, (const float*)b2, M, variant, (float*)out);
     return (int)hipGetLastError();
 }
-
-int ma_device_sync() { return (int)hipDeviceSynchronize(); }
 
 }  // extern "C"

@@ -62,6 +62,7 @@
 #include <stdlib.h>
 
 #include "curve_common.h"
+#include "mc_step.h"
 #include "row_fold.h"
 
 #define WAVE 64
@@ -87,7 +88,7 @@ typedef unsigned long long ull;
 // step like the records; the tail reads exactly `grid` of them.
 #define ONEPASS_FLAG_OFF(C) (ONEPASS_REC_OFF(C) + 2 * ONEPASS_GRID_MAX)
 #define ONEPASS_CS_WORDS(C) (ONEPASS_FLAG_OFF(C) + ONEPASS_GRID_MAX / 8)
-#define ONEPASS_TAIL_GRID_DEFAULT 4096  // blocks of k_onepass_tail, see ma_mc_onepass_update
+#define ONEPASS_TAIL_GRID_DEFAULT 4096  // blocks of k_onepass_tail, see onepass_step
 
 // TOPK: the optional top-k stat slot (second scratch tp2|fp2|fn2, see
 // count_row_topk). A template parameter, so the instantiation without the slot
@@ -492,34 +493,29 @@ static int onepass_tail_cap() {
 
 }  // extern "C"
 
-// Everything of a step that stays the same from one step to the next: shape,
-// thresholds and the addresses of the states and scratches. The caller owns
-// the memory behind the addresses and keeps it alive as long as the plan.
+// Everything of a step that stays the same from one step to the next: the
+// step record (mc_step.h), copied by value, plus the curve leader's part. The
+// caller owns the memory behind the addresses and keeps it alive as long as
+// the plan.
 struct OnepassPlan {
-    int dtype, nv, T, uniform, has_ignore;
-    ll C, ignore_index;
+    McStep st;
+    int dtype, nv, T, uniform;
     float t0, inv_step;
-    ull *scratch, *confmat, *hist, *cscratch;
-    ll *tp, *fp, *tn, *fn, *correct, *total;
-    float *rowmax, *rowinv;
-    unsigned int* epoch_buf;
+    ull *hist, *cscratch;
     const float* thresholds;
-    // top-k stat slot (ma_onepass_plan_set_topk); topk == 0: no slot
-    int topk;
-    ull* scratch2;  // [tp_k|fp_k|fn_k], 3*C u64
-    ll *tp2, *fp2, *tn2, *fn2;
 };
 
 template <typename T_, int NV, bool TOPK>
 static void onepass_launch_main(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
                                 const ll* target, ll B, uint4* records, unsigned char* flags) {
-    ull* sc = p.scratch;
-    ull* sc2 = TOPK ? p.scratch2 : nullptr;
+    const McStep& st = p.st;
+    ull* sc = st.counts;
+    ull* sc2 = TOPK ? st.topk_counts : nullptr;
     k_mc_onepass<T_, NV, TOPK><<<grid, 256, (size_t)p.T * sizeof(float), s>>>(
-        (const uint4*)preds, target, B, p.C, p.ignore_index, p.has_ignore, sc, sc + p.C,
-        sc + 2 * p.C, p.confmat, p.rowmax, p.rowinv, p.thresholds, p.T, p.uniform, p.t0,
-        p.inv_step, p.hist, p.cscratch, records, flags, p.topk, sc2, TOPK ? sc2 + p.C : nullptr,
-        TOPK ? sc2 + 2 * p.C : nullptr);
+        (const uint4*)preds, target, B, st.C, st.ignore_index, (int)st.has_ignore, sc, sc + st.C,
+        sc + 2 * st.C, st.confmat, st.rowmax, st.rowinv, p.thresholds, p.T, p.uniform, p.t0,
+        p.inv_step, p.hist, p.cscratch, records, flags, (int)st.k, sc2,
+        TOPK ? sc2 + st.C : nullptr, TOPK ? sc2 + 2 * st.C : nullptr);
 }
 template <typename T_, bool TOPK>
 static void onepass_launch_nv(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
@@ -533,11 +529,13 @@ template <typename T_, bool TOPK>
 static void onepass_launch_tail(const OnepassPlan& p, hipStream_t s, int tgrid, int grid,
                                 const void* preds, const ll* target, ll B, int c_chunk,
                                 const uint4* records, const unsigned char* flags) {
+    const McStep& st = p.st;
     k_onepass_tail<T_, TOPK><<<tgrid, 256, (size_t)p.T * sizeof(float), s>>>(
-        records, flags, grid, p.scratch, p.C, B, p.tp, p.fp, p.tn, p.fn, p.correct, p.total,
-        p.epoch_buf, p.cscratch, p.thresholds, p.T, p.hist, (const T_*)preds, target,
-        p.ignore_index, p.has_ignore, p.uniform, p.t0, p.inv_step, c_chunk,
-        (const float*)p.rowmax, (const float*)p.rowinv, p.scratch2, p.tp2, p.fp2, p.tn2, p.fn2);
+        records, flags, grid, st.counts, st.C, B, st.tp, st.fp, st.tn, st.fn, st.correct, st.total,
+        st.epoch_buf, p.cscratch, p.thresholds, p.T, p.hist, (const T_*)preds, target,
+        st.ignore_index, (int)st.has_ignore, p.uniform, p.t0, p.inv_step, c_chunk,
+        (const float*)st.rowmax, (const float*)st.rowinv, st.topk_counts, st.tp_k, st.fp_k,
+        st.tn_k, st.fn_k);
 }
 // the dtype and slot dispatch of both kernels, written once
 template <bool TOPK>
@@ -560,12 +558,12 @@ static int onepass_step(const OnepassPlan& p, hipStream_t s, uintptr_t preds, ui
                         ll B) {
     if (preds & 15) return -103;
     if (B < 0 || B >= (1LL << 31)) return -101;  // u32 counts in the records
-    const ll C = p.C;
+    const ll C = p.st.C;
     uint4* records = (uint4*)(p.cscratch + ONEPASS_REC_OFF(C));
     unsigned char* flags = (unsigned char*)(p.cscratch + ONEPASS_FLAG_OFF(C));
     const int grid = B > 0 ? onepass_grid(B) : 0;
     if (B > 0) {
-        if (p.topk > 0) onepass_launch_main_dt<true>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
+        if (p.st.k > 0) onepass_launch_main_dt<true>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
         else onepass_launch_main_dt<false>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
@@ -589,75 +587,36 @@ static int onepass_step(const OnepassPlan& p, hipStream_t s, uintptr_t preds, ui
     const ll eblocks = (C + 255) / 256;
     if (tg < eblocks) tg = eblocks;
     const int tgrid = (int)((tg + 7) / 8 * 8);  // multiple of 8: block % 8 is the XCD
-    if (p.topk > 0) onepass_launch_tail_dt<true>(p, s, tgrid, grid, (const void*)preds, (const ll*)target, B, c_chunk, records, flags);
+    if (p.st.k > 0) onepass_launch_tail_dt<true>(p, s, tgrid, grid, (const void*)preds, (const ll*)target, B, c_chunk, records, flags);
     else onepass_launch_tail_dt<false>(p, s, tgrid, grid, (const void*)preds, (const ll*)target, B, c_chunk, records, flags);
     return (int)hipGetLastError();
-}
-
-// Fill a plan; -103 for a shape the kernel does not cover or a missing /
-// misaligned buffer. scratch = stat scratch [tp|fp|fn|valid] (3*C+1 u64; the
-// valid slot is not used here), cscratch = curve scratch [P|N1|N0
-// copies|records] (ma_mc_onepass_scratch_words(C) u64); the counters of both
-// are zero before the first step and zero again after every tail, the records
-// need no zeroing. correct/total may be 0 (no exact-match leader).
-static int onepass_plan_fill(OnepassPlan& p, int dtype, ll C, ll ignore_index, int has_ignore,
-                             uintptr_t scratch, uintptr_t confmat, uintptr_t tp, uintptr_t fp,
-                             uintptr_t tn, uintptr_t fn, uintptr_t correct, uintptr_t total,
-                             uintptr_t rowmax, uintptr_t rowinv, uintptr_t epoch_buf,
-                             uintptr_t thresholds, int T, int uniform, float t0, float inv_step,
-                             uintptr_t hist, uintptr_t cscratch) {
-    const int nv = ma_mc_onepass_nv(dtype, C, T);
-    if (nv == 0 || (cscratch & 15) || !scratch || !cscratch || !hist || !rowmax || !rowinv ||
-        !epoch_buf || !thresholds)
-        return -103;
-    p.dtype = dtype; p.nv = nv; p.T = T; p.uniform = uniform; p.has_ignore = has_ignore;
-    p.C = C; p.ignore_index = ignore_index; p.t0 = t0; p.inv_step = inv_step;
-    p.scratch = (ull*)scratch; p.confmat = (ull*)confmat; p.hist = (ull*)hist;
-    p.cscratch = (ull*)cscratch;
-    p.tp = (ll*)tp; p.fp = (ll*)fp; p.tn = (ll*)tn; p.fn = (ll*)fn;
-    p.correct = (ll*)correct; p.total = (ll*)total;
-    p.rowmax = (float*)rowmax; p.rowinv = (float*)rowinv;
-    p.epoch_buf = (unsigned int*)epoch_buf; p.thresholds = (const float*)thresholds;
-    p.topk = 0; p.scratch2 = nullptr; p.tp2 = p.fp2 = p.tn2 = p.fn2 = nullptr;
-    return 0;
 }
 
 extern "C" {
 
 // Step plan: create once per set of states, step every update (stream, preds,
 // target and B are all that changes), destroy when the states are replaced.
-// *handle is written only on success.
-int ma_onepass_plan_create(int dtype, ll C, ll ignore_index, int has_ignore, uintptr_t scratch,
-                           uintptr_t confmat, uintptr_t tp, uintptr_t fp, uintptr_t tn,
-                           uintptr_t fn, uintptr_t correct, uintptr_t total, uintptr_t rowmax,
-                           uintptr_t rowinv, uintptr_t epoch_buf, uintptr_t thresholds, int T,
-                           int uniform, float t0, float inv_step, uintptr_t hist,
-                           uintptr_t cscratch, unsigned long long* handle) {
-    OnepassPlan* p = new OnepassPlan;
-    const int rc = onepass_plan_fill(*p, dtype, C, ignore_index, has_ignore, scratch, confmat, tp,
-                                     fp, tn, fn, correct, total, rowmax, rowinv, epoch_buf,
-                                     thresholds, T, uniform, t0, inv_step, hist, cscratch);
-    if (rc != 0) { delete p; return rc; }
-    *handle = (unsigned long long)(uintptr_t)p;
-    return 0;
-}
-
-// Give a plan the top-k stat slot: every later step also counts, per valid row,
-// the effective prediction "target if it ranks inside the top k, else the
-// argmax" into scratch2 = [tp_k|fp_k|fn_k] (3*C u64, zero before the first step
-// and zero again after every tail) and applies it to the four states. k == 0
-// takes the slot away again. -103 for k < 0 or a missing buffer.
-int ma_onepass_plan_set_topk(uintptr_t handle, int k, uintptr_t scratch2, uintptr_t tp2,
-                             uintptr_t fp2, uintptr_t tn2, uintptr_t fn2) {
-    if (!handle || k < 0) return -103;
-    OnepassPlan* p = (OnepassPlan*)handle;
-    if (k == 0) {
-        p->topk = 0; p->scratch2 = nullptr; p->tp2 = p->fp2 = p->tn2 = p->fn2 = nullptr;
-        return 0;
-    }
-    if (!scratch2 || !tp2 || !fp2 || !tn2 || !fn2) return -103;
-    p->topk = k; p->scratch2 = (ull*)scratch2;
-    p->tp2 = (ll*)tp2; p->fp2 = (ll*)fp2; p->tn2 = (ll*)tn2; p->fn2 = (ll*)fn2;
+// -103 for a shape the kernel does not cover or a missing / misaligned buffer;
+// *handle is written only on success. Of the record the plan needs the count
+// block (its valid slot is not used here), the stat states, the row statistics
+// and the epoch buffer; confmat, correct/total and the top-k slot (k > 0: every
+// step also counts and applies it) are optional. cscratch = curve scratch
+// [P|N1|N0 copies|records] (ma_mc_onepass_scratch_words(C) u64). The counters
+// of all blocks are zero before the first step and zero again after every
+// tail, the records need no zeroing.
+int ma_onepass_plan_create(const McStep* st, int dtype, uintptr_t thresholds, int T, int uniform,
+                           float t0, float inv_step, uintptr_t hist, uintptr_t cscratch,
+                           unsigned long long* handle) {
+    const int nv = ma_mc_onepass_nv(dtype, st->C, T);
+    if (nv == 0 || (cscratch & 15) || !cscratch || !hist || !thresholds || !st->counts ||
+        !st->tp || !st->fp || !st->tn || !st->fn || !st->rowmax || !st->rowinv || !st->epoch_buf ||
+        !st->correct != !st->total || st->k < 0)
+        return -103;
+    if (st->k > 0 && (!st->topk_counts || !st->tp_k || !st->fp_k || !st->tn_k || !st->fn_k))
+        return -103;
+    *handle = (unsigned long long)(uintptr_t) new OnepassPlan{
+        *st, dtype, nv, T, uniform, t0, inv_step, (ull*)hist, (ull*)cscratch,
+        (const float*)thresholds};
     return 0;
 }
 
@@ -668,24 +627,5 @@ int ma_onepass_plan_step(uintptr_t handle, uintptr_t stream, uintptr_t preds, ui
 }
 
 void ma_onepass_plan_destroy(uintptr_t handle) { delete (OnepassPlan*)handle; }
-
-// One step without a kept plan: the same fill and the same step as
-// create / step / destroy, so every caller goes through the same launches and
-// gets the same codes.
-int ma_mc_onepass_update(uintptr_t stream, uintptr_t preds, int dtype, uintptr_t target, ll B,
-                         ll C, ll ignore_index, int has_ignore, uintptr_t scratch,
-                         uintptr_t confmat, uintptr_t tp, uintptr_t fp, uintptr_t tn, uintptr_t fn,
-                         uintptr_t correct, uintptr_t total, uintptr_t rowmax, uintptr_t rowinv,
-                         uintptr_t epoch_buf, uintptr_t thresholds, int T, int uniform, float t0,
-                         float inv_step, uintptr_t hist, uintptr_t cscratch) {
-    unsigned long long h = 0;
-    const int rc = ma_onepass_plan_create(dtype, C, ignore_index, has_ignore, scratch, confmat, tp,
-                                          fp, tn, fn, correct, total, rowmax, rowinv, epoch_buf,
-                                          thresholds, T, uniform, t0, inv_step, hist, cscratch, &h);
-    if (rc != 0) return rc;
-    const int rs = ma_onepass_plan_step((uintptr_t)h, stream, preds, target, B);
-    ma_onepass_plan_destroy((uintptr_t)h);
-    return rs;
-}
 
 }  // extern "C"

@@ -16,18 +16,21 @@
 template <typename T>
 inline constexpr bool is_bf16_v = std::is_same<T, unsigned short>::value;
 
-// KERNEL<float> for dtype code 0, KERNEL<unsigned short> for every other code,
-// with the argument list written once; DT names the element type inside it.
-#define LAUNCH_BY_DTYPE(dtype, KERNEL, grid, block, shmem, stream, ...)                            \
+// One statement with DT = float for dtype code 0 and DT = unsigned short for
+// every other code, written once. LAUNCH_BY_DTYPE is the common case of it:
+// KERNEL<DT> with the argument list written once.
+#define FOR_DTYPE(dtype, ...)                                                                      \
     do {                                                                                           \
         if ((dtype) == 0) {                                                                        \
             typedef float DT;                                                                      \
-            KERNEL<DT><<<grid, block, shmem, stream>>>(__VA_ARGS__);                               \
+            __VA_ARGS__;                                                                           \
         } else {                                                                                   \
             typedef unsigned short DT;                                                             \
-            KERNEL<DT><<<grid, block, shmem, stream>>>(__VA_ARGS__);                               \
+            __VA_ARGS__;                                                                           \
         }                                                                                          \
     } while (0)
+#define LAUNCH_BY_DTYPE(dtype, KERNEL, grid, block, shmem, stream, ...)                            \
+    FOR_DTYPE(dtype, KERNEL<DT><<<grid, block, shmem, stream>>>(__VA_ARGS__))
 
 __device__ __forceinline__ float bf16_to_f32(unsigned short u) {
     unsigned int v = ((unsigned int)u) << 16;

@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes
 import operator
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -32,11 +32,12 @@ def _load() -> Optional[ctypes.CDLL]:
         _LOAD_ERR = f"HIP kernel library not built at {p}. Run `python -m metrics_amd.csrc.build`."
         return None
     try:
-        _LIB = ctypes.CDLL(str(p))
+        lib = ctypes.CDLL(str(p))
     except OSError as err:
         _LOAD_ERR = f"Failed to load {p}: {err}"
         return None
-    _declare_argtypes(_LIB)
+    _declare_argtypes(lib)  # raises on a record mismatch: such a library is never published
+    _LIB = lib
     return _LIB
 
 
@@ -46,11 +47,70 @@ _I = ctypes.c_int
 _F = ctypes.c_float
 _D = ctypes.c_double
 
+
+class McStepTensors(NamedTuple):
+    """The tensor objects one multiclass step works on, by name. Every optional
+    group is None when absent."""
+
+    counts: Tensor  # [tp|fp|fn|valid], (3*C+1,) int64: the count pass fills it, the apply pass zeroes it
+    confmat: Optional[Tensor] = None  # (C, C) state, counted into directly
+    tp: Optional[Tensor] = None  # the four stat states, (C,) each
+    fp: Optional[Tensor] = None
+    tn: Optional[Tensor] = None
+    fn: Optional[Tensor] = None
+    correct: Optional[Tensor] = None  # the exact-match states
+    total: Optional[Tensor] = None
+    rowstats: Optional[Tensor] = None  # (2, >=B) float32 [rowmax; rowinv], with epoch_buf
+    epoch_buf: Optional[Tensor] = None  # the curve leader's device epoch E
+    topk_counts: Optional[Tensor] = None  # [tp_k|fp_k|fn_k], (3*C,) int64, with the four states below
+    tp_k: Optional[Tensor] = None
+    fp_k: Optional[Tensor] = None
+    tn_k: Optional[Tensor] = None
+    fn_k: Optional[Tensor] = None
+
+
+class McStep(ctypes.Structure):
+    """Mirror of ``McStep`` in csrc/mc_step.h, field for field: the fixed part
+    of one multiclass step as the native count / apply / plan entries read it.
+    ``_load`` holds field names, order and size against the header,
+    tests/unittests/test_mc_step_record.py every field's offset as well."""
+
+    _fields_ = [
+        ("C", _LL), ("ignore_index", _LL), ("has_ignore", _LL),
+        ("counts", _U64), ("confmat", _U64),
+        ("tp", _U64), ("fp", _U64), ("tn", _U64), ("fn", _U64),
+        ("correct", _U64), ("total", _U64),
+        ("rowmax", _U64), ("rowinv", _U64), ("epoch_buf", _U64),
+        ("k", _LL), ("topk_counts", _U64),
+        ("tp_k", _U64), ("fp_k", _U64), ("tn_k", _U64), ("fn_k", _U64),
+    ]
+
+
+_STEP_P = ctypes.POINTER(McStep)
+
+
+def mc_step(num_classes: int, ignore_index: Optional[int], t: McStepTensors, k: int = 0) -> McStep:
+    """The record of one step over ``num_classes`` classes and the tensors
+    ``t`` (``k`` > 0 turns the top-k slot on). It holds bare addresses: whoever
+    keeps the record keeps ``t`` next to it."""
+    rec = McStep(C=num_classes, ignore_index=ignore_index if ignore_index is not None else 0,
+                 has_ignore=ignore_index is not None, k=k)
+    for name, x in zip(t._fields, t):
+        if x is not None and name != "rowstats":
+            setattr(rec, name, x.data_ptr())
+    if t.rowstats is not None:
+        rec.rowmax = t.rowstats.data_ptr()
+        rec.rowinv = rec.rowmax + 4 * t.rowstats.shape[1]
+    return rec
+
+
 _SIGNATURES = {
-    "ma_mc_stat_logits": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
-    "ma_mc_stat_logits_topk": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _U64, _U64, _U64],
+    "ma_mc_stat_logits": [_U64, _STEP_P, _U64, _I, _U64, _LL, _U64],
     "ma_mc_stat_topk_covers": [_LL],
-    "ma_mc_stat_labels": [_U64, _U64, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64],
+    "ma_mc_stat_labels": [_U64, _STEP_P, _U64, _U64, _LL],
+    "ma_mc_stat_apply": [_U64, _STEP_P, _LL, _I],
+    "ma_mc_step_dump": [_STEP_P, ctypes.POINTER(_U64)],
+    "ma_mc_step_sizeof": [],
     "ma_bincount": [_U64, _U64, _LL, _LL, _U64],
     "ma_binary_stat": [_U64, _U64, _I, _U64, _LL, _F, _LL, _I, _U64, _U64],
     "ma_multilabel_stat": [_U64, _U64, _I, _U64, _LL, _LL, _F, _LL, _I, _U64, _U64],
@@ -63,17 +123,10 @@ _SIGNATURES = {
     "ma_compute_plan_create": [_LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _F, _LL, ctypes.POINTER(ctypes.c_ulonglong)],
     "ma_compute_plan_step": [_U64, _U64, _I, _U64, _U64],
     "ma_linear_stat_multi": [_U64, _U64, _U64, _U64, _U64, _LL, _I, _U64, _U64],
-    "ma_apply_stat_deltas": [_U64, _U64, _LL, _U64, _U64, _U64, _U64, _U64],
-    "ma_exact_apply": [_U64, _U64, _LL, _LL, _I, _U64, _U64],
     "ma_mc_onepass_nv": [_I, _LL, _I],
     "ma_mc_onepass_scratch_words": [_LL],
-    "ma_mc_onepass_update": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64],
-    "ma_onepass_plan_create": [_I, _LL, _LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _I, _F, _F, _U64, _U64, ctypes.POINTER(ctypes.c_ulonglong)],
+    "ma_onepass_plan_create": [_STEP_P, _I, _U64, _I, _I, _F, _F, _U64, _U64, ctypes.POINTER(ctypes.c_ulonglong)],
     "ma_onepass_plan_step": [_U64, _U64, _U64, _U64, _LL],
-    "ma_onepass_plan_set_topk": [_U64, _I, _U64, _U64, _U64, _U64, _U64],
-    "ma_apply_stat_exact": [_U64, _U64, _LL, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
-    "ma_apply_stat_exact_topk": [_U64, _U64, _LL, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
-    "ma_apply_stat_deltas_topk": [_U64, _U64, _LL, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
     "ma_curve_auc_from_confmat": [_U64, _U64, _I, _LL, _I, _U64, _U64],
     "ma_err_reduce": [_U64, _U64, _U64, _I, _LL, _I, _D, _U64, _I, _I, _U64],
     "ma_box_iou": [_U64, _U64, _LL, _U64, _LL, _I, _U64],
@@ -99,6 +152,19 @@ def _declare_argtypes(lib: ctypes.CDLL) -> None:
     lib.ma_onepass_plan_destroy.restype = None
     lib.ma_compute_plan_destroy.argtypes = [_U64]
     lib.ma_compute_plan_destroy.restype = None
+    lib.ma_mc_step_field_names.argtypes = []
+    lib.ma_mc_step_field_names.restype = ctypes.c_char_p
+    mirror = [name for name, _ in McStep._fields_]
+    if mc_step_native_fields(lib) != mirror or lib.ma_mc_step_sizeof() != ctypes.sizeof(McStep):
+        raise RuntimeError(
+            f"McStep: the Python mirror {mirror} and csrc/mc_step.h {mc_step_native_fields(lib)} differ in"
+            " field names, order or size; rebuild the library"
+        )
+
+
+def mc_step_native_fields(lib: ctypes.CDLL) -> list:
+    """The field names of the native ``McStep`` in declaration order."""
+    return lib.ma_mc_step_field_names().decode().rstrip(",").split(",")
 
 
 def hip_available() -> bool:
@@ -151,76 +217,52 @@ def _to_supported(t: Tensor) -> Tensor:
     return t
 
 
-def _launch_mc_stat(
-    preds: Tensor, target: Tensor, C: int, ignore_index: Optional[int],
-    tp_ptr: int, fp_ptr: int, fn_ptr: int, confmat_ptr: int, valid_ptr: int,
-    argmax_ptr: int = 0, rowstats=None, topk=None,
-) -> int:
-    """The one stat launch every multiclass update shares: ``ma_mc_stat_logits``
-    for (B, C) float ``preds`` (fused row-argmax), ``ma_mc_stat_labels`` for
-    integer label ``preds``. Counts land in the (C,) u64 buffers behind the
-    pointers (``confmat_ptr``/``argmax_ptr`` may be 0); ``rowstats`` =
-    (rowmax, rowinv, epoch_buf) also emits the softmax row statistics (logits
-    only). ``topk`` = (k, scratch2) adds the top-k slot (logits only, C the
-    slot covers): its counts land in the (3*C,) ``scratch2``. Returns B, the
-    number of samples."""
+def mc_step_count(rec: McStep, preds: Tensor, target: Tensor, argmax: Optional[Tensor] = None) -> int:
+    """The count launch every multiclass update shares: ``ma_mc_stat_logits``
+    for (B, C) float ``preds`` (fused row-argmax, plus row statistics and the
+    top-k slot where ``rec`` has them), ``ma_mc_stat_labels`` for integer label
+    ``preds``. Counts land in the count block(s) of ``rec``, whose owner keeps
+    them alive. Returns B, the number of samples."""
     lib = _lib()
-    ign = (ignore_index if ignore_index is not None else 0, 1 if ignore_index is not None else 0)
     if preds.ndim == 2 and preds.is_floating_point():
         preds = _to_supported(preds).contiguous()
         target = target.contiguous().long()
         B = preds.shape[0]
-        assert preds.shape[1] == C, "preds must be (B, num_classes)"
-        rs = [t.data_ptr() for t in rowstats] if rowstats is not None else [0, 0, 0]
-        if topk is not None:
-            k, scratch2 = topk
-            p2 = scratch2.data_ptr()
-            rc = lib.ma_mc_stat_logits_topk(
-                _stream(), preds.data_ptr(), _dtype_code(preds), target.data_ptr(), B, C, *ign,
-                tp_ptr, fp_ptr, fn_ptr, confmat_ptr, valid_ptr, argmax_ptr, *rs,
-                k, p2, p2 + 8 * C, p2 + 16 * C,
-            )
-            _check(rc, "ma_mc_stat_logits_topk")
-            return B
+        assert preds.shape[1] == rec.C, "preds must be (B, num_classes)"
         rc = lib.ma_mc_stat_logits(
-            _stream(), preds.data_ptr(), _dtype_code(preds), target.data_ptr(), B, C, *ign,
-            tp_ptr, fp_ptr, fn_ptr, confmat_ptr, valid_ptr, argmax_ptr, *rs,
+            _stream(), rec, preds.data_ptr(), _dtype_code(preds), target.data_ptr(), B,
+            argmax.data_ptr() if argmax is not None else 0,
         )
         _check(rc, "ma_mc_stat_logits")
     else:
         preds = preds.contiguous().long().flatten()
         target = target.contiguous().long().flatten()
         B = preds.numel()
-        rc = lib.ma_mc_stat_labels(
-            _stream(), preds.data_ptr(), target.data_ptr(), B, C, *ign,
-            tp_ptr, fp_ptr, fn_ptr, confmat_ptr, valid_ptr,
-        )
+        rc = lib.ma_mc_stat_labels(_stream(), rec, preds.data_ptr(), target.data_ptr(), B)
         _check(rc, "ma_mc_stat_labels")
     return B
 
 
-def _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch: Tensor, confmat_ptr=0, rowstats=None,
-                            topk=None) -> int:
-    """:func:`_launch_mc_stat` into a (3*C+1,) int64 scratch laid out [tp|fp|fn|valid]."""
-    p = scratch.data_ptr()
-    return _launch_mc_stat(preds, target, C, ignore_index, p, p + 8 * C, p + 16 * C, confmat_ptr,
-                           p + 24 * C, rowstats=rowstats, topk=topk)
+def mc_step_apply(rec: McStep, B: int, close_epoch: bool = False) -> None:
+    """The apply launch (``ma_mc_stat_apply``, one block): the count block(s)
+    of ``rec`` are added to its stat states and zeroed, the exact-match states
+    get their share of the ``B`` rows, and ``close_epoch`` closes the curve
+    leader's device epoch in the same launch."""
+    rc = _lib().ma_mc_stat_apply(_stream(), rec, B, 1 if close_epoch else 0)
+    _check(rc, "ma_mc_stat_apply")
 
 
 def _fresh_mc_stat(preds, target, C, ignore_index, want_confmat, argmax: Optional[Tensor] = None):
-    """:func:`_launch_mc_stat` into freshly zeroed per-class tensors."""
+    """:func:`mc_step_count` into one freshly zeroed count block; tp, fp, fn
+    and valid are views of it."""
     dev = preds.device
-    tp = torch.zeros(C, dtype=torch.long, device=dev)
-    fp = torch.zeros(C, dtype=torch.long, device=dev)
-    fn = torch.zeros(C, dtype=torch.long, device=dev)
-    valid = torch.zeros(1, dtype=torch.long, device=dev)
-    confmat = torch.zeros(C, C, dtype=torch.long, device=dev) if want_confmat else None
-    _launch_mc_stat(
-        preds, target, C, ignore_index, tp.data_ptr(), fp.data_ptr(), fn.data_ptr(),
-        confmat.data_ptr() if confmat is not None else 0, valid.data_ptr(),
-        argmax.data_ptr() if argmax is not None else 0,
+    t = McStepTensors(
+        counts=torch.zeros(3 * C + 1, dtype=torch.long, device=dev),
+        confmat=torch.zeros(C, C, dtype=torch.long, device=dev) if want_confmat else None,
     )
-    return tp, fp, fn, valid, confmat
+    mc_step_count(mc_step(C, ignore_index, t), preds, target, argmax)
+    tp, fp, fn, valid = t.counts.split((C, C, C, 1))
+    return tp, fp, fn, valid, t.confmat
 
 
 def mc_stat_logits(
@@ -354,16 +396,48 @@ def curve_kernels_cover(num_thresholds: int) -> bool:
     return int(num_thresholds) <= CURVE_MAX_T
 
 
+def owner_buffer(owner, key: str, shape: tuple, dtype, device, zero: bool = True, grow: bool = False) -> Tensor:
+    """This owner's buffer under ``owner.__dict__[key]`` (one dtype per key):
+    allocated on first use (zeroed unless ``zero`` is False) and again when
+    device or shape no longer fit. ``grow``: a buffer at least ``shape`` in
+    every dimension fits (the row-statistics buffer only grows with the batch)."""
+    buf = owner.__dict__.get(key)
+    if buf is not None and buf.device == device:
+        have = buf.shape
+        if have == shape or (grow and len(have) == len(shape) and all(map(operator.ge, have, shape))):
+            return buf
+    buf = owner.__dict__[key] = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=device)
+    return buf
+
+
+def mc_count_block(owner, num_classes: int, device, key: str = "_hip_scratch", valid: bool = True) -> Tensor:
+    """The owner's zeroed count block [tp|fp|fn|valid] (without the valid slot:
+    the top-k block) that the apply pass leaves zeroed again."""
+    return owner_buffer(owner, key, (3 * num_classes + (1 if valid else 0),), torch.long, device)
+
+
+def rows_by_class(preds: Tensor, target: Tensor) -> Tuple[Tensor, Tensor]:
+    """(N, C, ...) float predictions as (rows, C) and everything else flat,
+    with the flat target: the layout the multiclass count kernels read."""
+    if preds.ndim == target.ndim + 1 and preds.is_floating_point():
+        C = preds.shape[1]
+        preds = preds.reshape(preds.shape[0], C, -1).movedim(1, -1).reshape(-1, C)
+    else:
+        preds = preds.reshape(-1)
+    return preds, target.reshape(-1)
+
+
+def _rowstats_buf(owner, B: int, device) -> Tensor:
+    """The owner's (2, >=B) float32 [rowmax; rowinv] buffer."""
+    return owner_buffer(owner, "_hip_rowstats_buf", (2, B), torch.float32, device, zero=False, grow=True)
+
+
 def _epoch_buf(device, owner=None) -> Tensor:
     """Device-epoch buffer E (2 x uint32). Owned per-METRIC when ``owner`` is
     given so independent metrics can update on parallel streams without racing
     on the protocol state; falls back to a per-device buffer otherwise."""
     if owner is not None:
-        buf = owner.__dict__.get("_hip_epoch_buf")
-        if buf is None or buf.device != device:
-            buf = torch.zeros(2, dtype=torch.int32, device=device)
-            owner.__dict__["_hip_epoch_buf"] = buf
-        return buf
+        return owner_buffer(owner, "_hip_epoch_buf", (2,), torch.int32, device)
     key = device.index
     buf = _FLAG_BUFS.get(key)
     if buf is None:
@@ -377,11 +451,7 @@ def _pooled_hist(outer: int, T: int, device, owner=None) -> Tensor:
     it in-flight after consuming it (zero_hist=1), so reuse needs no fill.
     Owned per-METRIC when ``owner`` is given (parallel-stream safety)."""
     if owner is not None:
-        buf = owner.__dict__.get("_hip_hist_buf")
-        if buf is None or buf.device != device or buf.shape != (outer, T + 1, 2):
-            buf = torch.zeros(outer, T + 1, 2, dtype=torch.long, device=device)
-            owner.__dict__["_hip_hist_buf"] = buf
-        return buf
+        return owner_buffer(owner, "_hip_hist_buf", (outer, T + 1, 2), torch.long, device)
     key = (outer, T, device.index)
     buf = _HIST_POOL.get(key)
     if buf is None:
@@ -959,10 +1029,7 @@ def curve_hist_into_confmat(
         hist = _pooled_hist(C, T, dev, owner)
         if norm == "softmax":
             if owner is not None:
-                rbuf = owner.__dict__.get("_hip_rowstats_buf")
-                if rbuf is None or rbuf.device != dev or rbuf.shape[1] < B:
-                    rbuf = torch.empty(2, B, dtype=torch.float32, device=dev)
-                    owner.__dict__["_hip_rowstats_buf"] = rbuf
+                rbuf = _rowstats_buf(owner, B, dev)
             else:
                 rkey = (B, dev.index)
                 rbuf = _ROWSTATS_POOL.get(rkey)
@@ -1119,25 +1186,13 @@ def mc_stat_into(
 ) -> None:
     """Fused stat-scores update accumulated DIRECTLY into the metric states.
 
-    ``scratch`` is a per-metric reusable (3*C+1,) int64 buffer; 2 launches
+    ``scratch`` is the metric's count block (:func:`mc_count_block`); 2 launches
     total (count + single-block apply): the apply kernel consumes AND zeroes
-    the whole scratch in one pass, so no fill kernel runs in steady state and
+    the whole block in one pass, so no fill kernel runs in steady state and
     no host-side epoch is needed (hipGraph-capturable).
     """
-    lib = _lib()
-    C = num_classes
-    _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch)
-    rc = lib.ma_apply_stat_deltas(
-        _stream(),
-        scratch.data_ptr(),
-        C,
-        tp.data_ptr(),
-        fp.data_ptr(),
-        tn.data_ptr(),
-        fn.data_ptr(),
-        0,
-    )
-    _check(rc, "ma_apply_stat_deltas")
+    rec = mc_step(num_classes, ignore_index, McStepTensors(counts=scratch, tp=tp, fp=fp, tn=tn, fn=fn))
+    mc_step_apply(rec, mc_step_count(rec, preds, target))
     _mark_kernel_mutated(tp)
 
 
@@ -1153,7 +1208,8 @@ def mc_confmat_into(
     harmlessly in int64).
     """
     assert confmat_state.is_contiguous()
-    _launch_mc_stat_scratch(preds, target, num_classes, ignore_index, dummy, confmat_state.data_ptr())
+    rec = mc_step(num_classes, ignore_index, McStepTensors(counts=dummy, confmat=confmat_state))
+    mc_step_count(rec, preds, target)
     _mark_kernel_mutated(confmat_state)
 
 
@@ -1164,22 +1220,11 @@ def mc_exact_into(
     """Exact-match (== row argmax equals target) accumulated into correct/total.
 
     Reuses the fused stat kernel's per-class tp counts: correct = sum(tp),
-    total = valid rows. Same (3*C+1,) self-zeroing scratch protocol as
+    total = valid rows. Same self-zeroing count block protocol as
     :func:`mc_stat_into`; 2 launches, zero fills in steady state.
     """
-    lib = _lib()
-    C = num_classes
-    _launch_mc_stat_scratch(preds, target, C, ignore_index, scratch)
-    rc = lib.ma_exact_apply(
-        _stream(),
-        scratch.data_ptr(),
-        C,
-        target.numel(),
-        1,
-        correct.data_ptr(),
-        total.data_ptr(),
-    )
-    _check(rc, "ma_exact_apply")
+    rec = mc_step(num_classes, ignore_index, McStepTensors(counts=scratch, correct=correct, total=total))
+    mc_step_apply(rec, mc_step_count(rec, preds, target))
 
 
 # Batched linear-stat plans: the stat metrics of a compute group share one
@@ -1271,75 +1316,14 @@ def mc_stat_topk_covers(num_classes: int) -> bool:
     return hit
 
 
-def mc_fused_collection_update(
-    preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int],
-    stat=None, confmat=None, exact=None, rowstats=None, defer_apply: bool = False,
-    bump_epoch_ptr: int = 0, topk=None,
-):
-    """Collection-level fused update: ONE pass over the (B, C) logits feeds the
-    stat-scores, confusion-matrix and exact-match leaders at once.
-
-    ``topk`` = (k, scratch2, tp, fp, tn, fn) — the top-k stat leader's slot:
-    the same pass counts its effective prediction into the (3*C,) ``scratch2``
-    and the same apply launch adds it to its states. Logits only, and only
-    where :func:`mc_stat_topk_covers` says so (the caller checks).
-
-    ``stat``  = (scratch, tp, fp, tn, fn) — required (owns the count scratch)
-    ``confmat`` = confmat state tensor (atomics accumulate directly) or None
-    ``exact`` = (correct, total) or None (reads the shared scratch BEFORE the
-    apply kernel consumes and zeroes it).
-    ``rowstats`` = (rowmax, rowinv, epoch_buf) or None: the same pass also
-    emits the softmax row statistics + out-of-range epoch flag that the
-    threshold-curve leader consumes (its own row-stats kernel is skipped).
-    """
-    lib = _lib()
-    C = num_classes
-    scratch, tp, fp, tn, fn = stat
-    B = _launch_mc_stat_scratch(
-        preds, target, C, ignore_index, scratch,
-        confmat.data_ptr() if confmat is not None else 0, rowstats,
-        topk=topk[:2] if topk is not None else None,
-    )
-
-    def _apply_pass() -> None:
-        # fused epilogue: stat-delta apply (+ exact-match) in ONE launch; when
-        # the lazy curve hist rides the same stream the caller defers this so
-        # it lands AFTER the hist kernel and closes the device epoch for free
-        # (a separate 1-thread bump kernel costs a full ~4us dispatch)
-        if topk is not None:
-            correct, total = exact if exact is not None else (None, None)
-            rc2 = lib.ma_apply_stat_exact_topk(
-                _stream(), scratch.data_ptr(), C, B if exact is not None else 0,
-                tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(),
-                correct.data_ptr() if correct is not None else 0,
-                total.data_ptr() if total is not None else 0, bump_epoch_ptr,
-                *(t.data_ptr() for t in topk[1:]),
-            )
-            _check(rc2, "ma_apply_stat_exact_topk")
-        elif exact is not None:
-            correct, total = exact
-            rc2 = lib.ma_apply_stat_exact(
-                _stream(), scratch.data_ptr(), C, B,
-                tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(),
-                correct.data_ptr(), total.data_ptr(), bump_epoch_ptr,
-            )
-            _check(rc2, "ma_apply_stat_exact")
-        else:
-            rc2 = lib.ma_apply_stat_deltas(
-                _stream(), scratch.data_ptr(), C,
-                tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(), bump_epoch_ptr,
-            )
-            _check(rc2, "ma_apply_stat_deltas")
-
-    if confmat is not None:
-        _mark_kernel_mutated(confmat)
-    _mark_kernel_mutated(tp)  # generation key for the batched linear-stat plan
-    if topk is not None:
-        _mark_kernel_mutated(topk[2])  # the top-k group's own linear-stat plan
-    if defer_apply:
-        return _apply_pass
-    _apply_pass()
-    return None
+def mc_step_mark_mutated(t: McStepTensors) -> None:
+    """Note the raw-pointer writes of one step for the version-keyed caches."""
+    if t.confmat is not None:
+        _mark_kernel_mutated(t.confmat)
+    if t.tp is not None:
+        _mark_kernel_mutated(t.tp)  # generation key for the batched linear-stat plan
+    if t.tp_k is not None:
+        _mark_kernel_mutated(t.tp_k)  # the top-k group's own linear-stat plan
 
 
 # One-pass fused-collection step (csrc/mc_onepass.hip). METRICS_AMD_ONEPASS:
@@ -1361,48 +1345,25 @@ def onepass_mode() -> int:
     return int(v) if v in ("0", "1", "2") else 1
 
 
-class _OnepassPlan:
-    """Native step plan of the one-pass update (``ma_onepass_plan_*``) with the
-    tensor objects whose addresses it holds. Destroyed with this object; a
-    copy or pickle of the owning metric gets None and builds its own."""
+class _NativePlan:
+    """A native plan handle with the tensor objects whose addresses the plan
+    holds: kept next to it, so none of the addresses can be freed or reused
+    under the plan, and ``is`` on each of them decides whether the plan still
+    fits. Destroyed with this object; a copy or pickle of the owner gets None
+    and builds its own."""
 
-    __slots__ = ("handle", "tensors", "scalars", "thr", "_destroy")
+    __slots__ = ("handle", "tensors", "_destroy")
 
-    def __init__(self, lib, tensors, scalars, thr: Tensor):
-        (scratch, tp, fp, tn, fn, confmat, correct, total, rowstats_buf, epoch_buf, hist, cs,
-         scratch2, tp2, fp2, tn2, fn2, _) = tensors
-        dt, C, T, ignore_index, k = scalars
-        uni, t0, inv_step = _uniform_params(thr)
-        rs_ptr = rowstats_buf.data_ptr()
-        handle = ctypes.c_ulonglong(0)
-        self.handle = 0
-        rc = lib.ma_onepass_plan_create(
-            dt, C, ignore_index if ignore_index is not None else 0,
-            1 if ignore_index is not None else 0,
-            scratch.data_ptr(), confmat.data_ptr() if confmat is not None else 0,
-            tp.data_ptr(), fp.data_ptr(), tn.data_ptr(), fn.data_ptr(),
-            correct.data_ptr() if correct is not None else 0,
-            total.data_ptr() if total is not None else 0,
-            rs_ptr, rs_ptr + 4 * rowstats_buf.shape[1], epoch_buf.data_ptr(),
-            thr.data_ptr(), T, uni, t0, inv_step, hist.data_ptr(), cs.data_ptr(),
-            ctypes.byref(handle),
-        )
-        _check(rc, "ma_onepass_plan_create")
-        self.handle = handle.value
-        self.tensors = tensors
-        self.scalars = scalars
-        self.thr = thr
-        self._destroy = lib.ma_onepass_plan_destroy
-        if k:  # the top-k slot
-            rc = lib.ma_onepass_plan_set_topk(
-                self.handle, k, scratch2.data_ptr(), tp2.data_ptr(), fp2.data_ptr(),
-                tn2.data_ptr(), fn2.data_ptr(),
-            )
-            _check(rc, "ma_onepass_plan_set_topk")
+    def _adopt(self, handle: int, tensors: tuple, destroy) -> None:
+        self.handle, self.tensors, self._destroy = handle, tensors, destroy
+
+    def fits(self, tensors) -> bool:
+        return all(map(operator.is_, self.tensors, tensors))
 
     def __del__(self):
-        if self.handle:
-            self._destroy(self.handle)
+        handle = getattr(self, "handle", 0)  # unset when the create call raised
+        if handle:
+            self._destroy(handle)
             self.handle = 0
 
     def __deepcopy__(self, memo):
@@ -1412,10 +1373,32 @@ class _OnepassPlan:
         return (type(None), ())
 
 
+class _OnepassPlan(_NativePlan):
+    """Native step plan of the one-pass update (``ma_onepass_plan_*``).
+    ``tensors`` = (*step tensors, hist, curve scratch, the leader's thresholds),
+    ``scalars`` = (dtype code, C, T, ignore_index, k), ``thr`` the float32
+    thresholds the plan reads."""
+
+    __slots__ = ("scalars", "thr_src", "thr")
+
+    def __init__(self, lib, step: McStepTensors, hist: Tensor, cs: Tensor, thr_src: Tensor, scalars, thr: Tensor):
+        dt, C, T, ignore_index, k = scalars
+        uni, t0, inv_step = _uniform_params(thr)
+        handle = ctypes.c_ulonglong(0)
+        rc = lib.ma_onepass_plan_create(
+            mc_step(C, ignore_index, step, k), dt,
+            thr.data_ptr(), T, uni, t0, inv_step, hist.data_ptr(), cs.data_ptr(), ctypes.byref(handle),
+        )
+        _check(rc, "ma_onepass_plan_create")
+        self._adopt(handle.value, (*step, hist, cs, thr_src), lib.ma_onepass_plan_destroy)
+        self.scalars = scalars
+        self.thr_src = thr_src
+        self.thr = thr
+
+
 def mc_onepass_update(
     preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int],
-    stat, confmat: Optional[Tensor], exact, rowstats_buf: Tensor, epoch_buf: Tensor, curve,
-    force: bool = False, topk=None,
+    step: McStepTensors, k: int, curve, force: bool = False,
 ) -> bool:
     """The whole fused-collection step (stat scores, confusion matrix, exact
     match, threshold-curve histogram) in ONE native call that reads the logits
@@ -1427,17 +1410,16 @@ def mc_onepass_update(
     (C <= 128, C not a multiple of the vector width, row too long for the
     register layout, unaligned storage) or, unless ``force``, lies below the
     C >= 5*T gate: the caller keeps the two-kernel path.
-    ``stat``/``exact`` as in :func:`mc_fused_collection_update`;
-    ``rowstats_buf`` is the (2, >=B) float32 rowmax/rowinv buffer, ``epoch_buf``
-    the curve leader's device-epoch buffer, ``curve`` the curve leader (owns the histogram and the curve scratch).
-    ``topk`` = (k, scratch2, tp, fp, tn, fn): the top-k stat leader's slot, as
-    in :func:`mc_fused_collection_update`; every shape the kernel covers has it.
+    ``step`` holds the participants (stat states, row statistics and epoch
+    buffer are required), ``k`` > 0 turns its top-k slot on (every shape the
+    kernel covers has it), ``curve`` is the curve leader (owns the histogram
+    and the curve scratch).
     """
     lib = _lib()
     C = num_classes
     plan = curve.__dict__.get("_hip_onepass_plan")
     thr_src = curve.thresholds
-    if plan is not None and plan.tensors[-1] is thr_src:
+    if plan is not None and plan.thr_src is thr_src:
         thr = plan.thr
     else:
         thr = thr_src.contiguous().float()
@@ -1455,38 +1437,24 @@ def mc_onepass_update(
         return False
     target = target.contiguous().long()
     dev = preds.device
-    scratch, tp, fp, tn, fn = stat
-    cs = curve.__dict__.get("_hip_onepass_scratch")
-    if cs is None or cs.device != dev or cs.numel() != cs_words:
-        # [P | N1 | N0 copies | per-block records | per-block flags]; the tail
-        # kernel re-zeroes the counters, records and flags are overwritten
-        # every step
-        cs = torch.zeros(cs_words, dtype=torch.long, device=dev)
-        curve.__dict__["_hip_onepass_scratch"] = cs
-    hist = _pooled_hist(C, T, dev, curve)
-    assert curve.confmat.is_contiguous()
     # The native plan holds the addresses of everything that stays the same
-    # from step to step; the tensor OBJECTS are kept next to it, so none of the
-    # addresses can be freed or reused under the plan, and `is` on each of them
-    # (plus dtype, C, T, ignore_index) decides whether the plan still fits.
-    # reset() and a move to another device replace the state tensors: the next
-    # step rebuilds the plan. Until then one stale set of states stays alive.
-    tensors = (
-        scratch, tp, fp, tn, fn, confmat,
-        exact[0] if exact is not None else None, exact[1] if exact is not None else None,
-        rowstats_buf, epoch_buf, hist, cs,
-        *(topk[1:] if topk is not None else (None,) * 5), thr_src,
-    )
-    scalars = (dt, C, T, ignore_index, topk[0] if topk is not None else 0)
-    if plan is None or plan.scalars != scalars or not all(map(operator.is_, plan.tensors, tensors)):
-        plan = curve.__dict__["_hip_onepass_plan"] = _OnepassPlan(lib, tensors, scalars, thr)
+    # from step to step (_NativePlan); dtype, C, T, ignore_index and k decide
+    # with them whether it still fits. reset() and a move to another device
+    # replace the state tensors: the next step rebuilds the plan. Until then
+    # one stale set of states stays alive.
+    own = curve.__dict__
+    tensors = (*step, own.get("_hip_hist_buf"), own.get("_hip_onepass_scratch"), thr_src)
+    scalars = (dt, C, T, ignore_index, k)
+    if plan is None or plan.scalars != scalars or not plan.fits(tensors):
+        # [P | N1 | N0 copies | per-block records | per-block flags]; the tail
+        # kernel re-zeroes the counters, records and flags are overwritten every step
+        cs = owner_buffer(curve, "_hip_onepass_scratch", (cs_words,), torch.long, dev)
+        hist = _pooled_hist(C, T, dev, curve)
+        assert curve.confmat.is_contiguous()
+        plan = own["_hip_onepass_plan"] = _OnepassPlan(lib, step, hist, cs, thr_src, scalars, thr)
     rc = lib.ma_onepass_plan_step(plan.handle, _stream(), preds.data_ptr(), target.data_ptr(), preds.shape[0])
     _check(rc, "ma_onepass_plan_step")
-    if confmat is not None:
-        _mark_kernel_mutated(confmat)
-    _mark_kernel_mutated(tp)
-    if topk is not None:
-        _mark_kernel_mutated(topk[2])
+    mc_step_mark_mutated(step)
     # same lazy protocol as curve_hist_into_confmat: the histogram accumulates,
     # the suffix/confmat materialization waits for the first state read
     curve.__dict__["_hip_lazy_meta"] = (C, T, 1)
@@ -1505,49 +1473,53 @@ def compute_plan_enabled() -> bool:
     return os.environ.get(COMPUTE_PLAN_ENV, "1") != "0"
 
 
-class _ComputePlan:
-    """Native compute plan (``ma_compute_plan_*``) with the tensor objects
-    whose addresses it holds: ``tensors`` are the state tensors (``is`` on each
-    decides whether the plan still fits), ``owned`` the plan's own buffers.
-    Destroyed with this object; a copy or pickle gets None."""
+class ComputeStates(NamedTuple):
+    """The state tensors a compute plan reads, None where a group is absent:
+    the stat states, the (C, C) confusion matrix, the exact-match states, the
+    (T, C, 2, 2) curve state and the curve leader's histogram."""
 
-    __slots__ = ("handle", "tensors", "owned", "auc_views", "n_formulas", "auc_stride", "device", "_destroy")
+    tp: Optional[Tensor] = None
+    fp: Optional[Tensor] = None
+    tn: Optional[Tensor] = None
+    fn: Optional[Tensor] = None
+    confmat: Optional[Tensor] = None
+    correct: Optional[Tensor] = None
+    total: Optional[Tensor] = None
+    curve_state: Optional[Tensor] = None
+    hist: Optional[Tensor] = None
 
-    def __init__(self, dev, C: int, T: int, stat, confmat, exact, curve, params, zero_division: float):
-        """stat = (tp, fp, tn, fn) | None, confmat = (C, C) state | None, exact =
-        (correct, total) | None, curve = (hist, (T, C, 2, 2) state) | None;
-        params = the 13 floats of every linear formula, flattened."""
+
+class _ComputePlan(_NativePlan):
+    """Native compute plan (``ma_compute_plan_*``): ``tensors`` are the
+    :class:`ComputeStates` it was built for, ``owned`` the plan's own buffers."""
+
+    __slots__ = ("owned", "auc_views", "n_formulas", "auc_stride", "device")
+
+    def __init__(self, dev, C: int, T: int, states: ComputeStates, params, zero_division: float):
+        """params = the 13 floats of every linear formula, flattened."""
         lib = _lib()
         self.device = dev
         n = len(params) // 13
+        has_curve = states.curve_state is not None
         params_dev = torch.tensor(params, dtype=torch.float32, device=dev) if n else None
-        cm_scratch = torch.zeros(3 * C, dtype=torch.long, device=dev) if confmat is not None else None
+        cm_scratch = torch.zeros(3 * C, dtype=torch.long, device=dev) if states.confmat is not None else None
         # each per-class vector starts 256-byte aligned, as a fresh tensor does
         self.auc_stride = (C + 63) // 64 * 64
-        auc = torch.empty(4, self.auc_stride, dtype=torch.float32, device=dev) if curve is not None else None
-        self.auc_views = tuple(auc[i, :C] for i in range(4)) if auc is not None else None
+        auc = torch.empty(4, self.auc_stride, dtype=torch.float32, device=dev) if has_curve else None
+        self.auc_views = tuple(auc[i, :C] for i in range(4)) if has_curve else None
         ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-        st = stat if stat is not None else (None,) * 4
-        ex = exact if exact is not None else (None,) * 2
-        cv = curve if curve is not None else (None,) * 2
         handle = ctypes.c_ulonglong(0)
-        self.handle = 0
         rc = lib.ma_compute_plan_create(
-            C, T, ptr(st[0]), ptr(st[1]), ptr(st[2]), ptr(st[3]), ptr(confmat), ptr(cm_scratch),
-            ptr(ex[0]), ptr(ex[1]), ptr(cv[0]), ptr(cv[1]),
+            C, T, ptr(states.tp), ptr(states.fp), ptr(states.tn), ptr(states.fn),
+            ptr(states.confmat), ptr(cm_scratch), ptr(states.correct), ptr(states.total),
+            ptr(states.hist) if has_curve else 0, ptr(states.curve_state),
             0,  # the lazy flush does not close an epoch: every update closed its own
             ptr(params_dev), n, float(zero_division), self.auc_stride, ctypes.byref(handle),
         )
         _check(rc, "ma_compute_plan_create")
-        self.handle = handle.value
-        # the order of _FusedMulticlassComputePlan._state_tensors, which fits() gets
-        self.tensors = (*st, confmat, *ex, cv[1], cv[0])
+        self._adopt(handle.value, states, lib.ma_compute_plan_destroy)
         self.owned = (params_dev, cm_scratch, auc)
         self.n_formulas = n
-        self._destroy = lib.ma_compute_plan_destroy
-
-    def fits(self, tensors) -> bool:
-        return all(map(operator.is_, self.tensors, tensors))
 
     def step(self, flush: bool):
         """One native call, at most three launches. Returns (out, auc): a fresh
@@ -1555,7 +1527,7 @@ class _ComputePlan:
         (C,) views ``(auroc, auroc weights, ap, ap weights)`` of the plan's own
         per-class buffer (None without a curve group; overwritten by the next
         step, so only reductions of them go to a caller)."""
-        auc = self.owned[2]
+        _, _, auc = self.owned
         # fresh per compute: views of it go to the caller and are never recycled
         out = torch.empty(self.n_formulas + 4, dtype=torch.float32, device=self.device)
         rc = _lib().ma_compute_plan_step(
@@ -1564,14 +1536,3 @@ class _ComputePlan:
         )
         _check(rc, "ma_compute_plan_step")
         return out, self.auc_views
-
-    def __del__(self):
-        if self.handle:
-            self._destroy(self.handle)
-            self.handle = 0
-
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (type(None), ())
