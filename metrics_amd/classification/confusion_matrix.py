@@ -149,6 +149,7 @@ class MulticlassConfusionMatrix(Metric):
 class MultilabelConfusionMatrix(Metric):
     """(L,2,2) confusion matrices for multilabel tasks (stateful)."""
 
+    _hip_fused_kind = "ml_confmat"
     is_differentiable = False
     higher_is_better = None
     full_state_update: bool = False

@@ -106,6 +106,7 @@ class MulticlassExactMatch(Metric):
 class MultilabelExactMatch(Metric):
     """Exact match for multilabel tasks (stateful)."""
 
+    _hip_fused_kind = "ml_exact"
     is_differentiable = False
     higher_is_better = True
     full_state_update: bool = False

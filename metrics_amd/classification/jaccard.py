@@ -127,6 +127,7 @@ class MulticlassJaccardIndex(Metric):
 class MultilabelJaccardIndex(Metric):
     """Jaccard index for multilabel tasks (stateful)."""
 
+    _hip_fused_kind = "ml_confmat"  # the (L, 2, 2) state and update of MultilabelConfusionMatrix
     is_differentiable = False
     higher_is_better = True
     full_state_update: bool = False

@@ -224,6 +224,7 @@ class MulticlassPrecisionRecallCurve(Metric):
 class MultilabelPrecisionRecallCurve(Metric):
     """PR curves for multilabel tasks (stateful)."""
 
+    _hip_fused_kind = "ml_curve"
     is_differentiable: bool = False
     higher_is_better: Optional[bool] = None
     full_state_update: bool = False

@@ -226,6 +226,7 @@ class MulticlassStatScores(_AbstractStatScores):
 class MultilabelStatScores(_AbstractStatScores):
     """Per-label tp/fp/tn/fn counts for multilabel tasks."""
 
+    _hip_fused_kind = "ml_stat"
     is_differentiable: bool = False
     higher_is_better: Optional[bool] = None
     full_state_update: bool = False

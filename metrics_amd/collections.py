@@ -234,6 +234,107 @@ class _FusedMulticlassUpdatePlan:
         return handled
 
 
+def _updates_as_marked(leader) -> bool:
+    """True if ``leader`` updates through the ``update`` of the class that
+    carries its ``_hip_fused_kind`` (a subclass with an update of its own is
+    not what the fused kernels implement)."""
+    for klass in type(leader).__mro__:
+        if "_hip_fused_kind" in klass.__dict__:
+            return type(leader).update is klass.update
+    return False
+
+
+class _FusedMultilabelUpdatePlan:
+    """Collection-level fusion for multilabel metrics: the leaders of the
+    stat-scores, confusion-matrix, exact-match and threshold-curve groups all
+    need the same per-element facts (label, ignored, ``x > cut``, bucket of the
+    probability), so ONE native call of two launches (``csrc/ml_step.hip``)
+    reads the (N, L) predictions and the int64 targets once and feeds all of
+    them. At least two participants; a stat leader is not required.
+
+    Inside a plan the confusion-matrix and exact-match leaders threshold with
+    the exact rule of the stat kernel (``x > logit(threshold)`` when the batch
+    is normalised) instead of comparing a rounded ``sigmoid(x)``: see
+    docs/PARITY.md. ``METRICS_AMD_FUSE_MULTILABEL=0`` builds no plan."""
+
+    def __init__(self, stat, confmat, exact, curve):
+        self.stat = stat
+        self.confmat = confmat
+        self.exact = exact
+        self.curve = curve
+        self.leaders = tuple(m for m in (stat, confmat, exact, curve) if m is not None)
+        self.num_labels = self.leaders[0].num_labels
+        self.ignore_index = self.leaders[0].ignore_index
+        # two participants and one curve leader at most: one of these exists
+        self.threshold = next(m.threshold for m in (stat, confmat, exact) if m is not None)
+        self.steps = 0
+        self.curve_steps = 0
+
+    @staticmethod
+    def build(collection) -> "Optional[_FusedMultilabelUpdatePlan]":
+        from metrics_amd.ops import _hip
+
+        if not _hip.fuse_multilabel_enabled():
+            return None
+        found = {"ml_stat": None, "ml_confmat": None, "ml_exact": None, "ml_curve": None}
+        for members in collection._groups.values():
+            leader = getattr(collection, members[0])
+            kind = getattr(type(leader), "_hip_fused_kind", None)
+            if kind not in found or found[kind] is not None:
+                continue  # the first leader of each kind; further groups stay on their own
+            if getattr(leader, "validate_args", True) or not _updates_as_marked(leader):
+                continue  # validations are skipped on the fused path
+            if getattr(leader, "multidim_average", "global") != "global":
+                continue
+            if kind == "ml_curve" and leader.thresholds is None:
+                continue
+            found[kind] = leader
+        stat, confmat, exact, curve = found["ml_stat"], found["ml_confmat"], found["ml_exact"], found["ml_curve"]
+        participants = [m for m in (stat, confmat, exact, curve) if m is not None]
+        if len(participants) < 2:
+            return None
+        if len({m.num_labels for m in participants}) != 1 or len({m.ignore_index for m in participants}) != 1:
+            return None
+        if len({float(m.threshold) for m in (stat, confmat, exact) if m is not None}) > 1:
+            return None
+        return _FusedMultilabelUpdatePlan(stat, confmat, exact, curve)
+
+    def try_run(self, *args: Any, **kwargs: Any) -> tuple:
+        """Run the fused step if the inputs qualify; returns the handled leaders
+        (empty tuple -> every leader updates on its own)."""
+        if kwargs or len(args) != 2:
+            return ()
+        preds, target = args
+        if not (isinstance(preds, Tensor) and isinstance(target, Tensor) and preds.is_cuda and target.is_cuda):
+            return ()
+        if preds.ndim != 2 or preds.dtype not in (torch.float32, torch.bfloat16) or not preds.is_contiguous():
+            return ()
+        if target.dtype != torch.long or target.shape != preds.shape or not target.is_contiguous():
+            return ()
+        if preds.shape[1] != self.num_labels or target.device != preds.device:
+            return ()
+        from metrics_amd.ops import _hip
+
+        if not _hip.hip_available():
+            return ()
+        stat, confmat, exact, curve = self.stat, self.confmat, self.exact, self.curve
+        # above the LDS gate the curve leader updates on its own, the rest still fuses
+        if curve is not None and curve.thresholds.numel() > _hip.ML_STEP_MAX_T:
+            curve = None
+        handled = self.leaders if curve is self.curve else tuple(m for m in self.leaders if m is not self.curve)
+        if len(handled) < 2:
+            return ()
+        if not _hip.ml_step_update(
+            preds, target, self.num_labels, self.ignore_index, self.threshold,
+            stat=stat, confmat=confmat, exact=exact, curve=curve,
+        ):
+            return ()
+        self.steps += 1
+        if curve is not None:
+            self.curve_steps += 1
+        return handled
+
+
 class _FusedMulticlassComputePlan:
     """Collection-level compute: every member that declares what it computes
     (``Metric._compute_plan_spec``) over the stat-scores, confusion-matrix,
@@ -423,6 +524,7 @@ class MetricCollection(ModuleDict):
     ) -> None:
         super().__init__()
         self._fused_plan: Any = False
+        self._fused_ml_plan: Any = False
         self._compute_plan: Any = False
         self.prefix = self._check_arg(prefix, "prefix")
         self.postfix = self._check_arg(postfix, "postfix")
@@ -455,6 +557,13 @@ class MetricCollection(ModuleDict):
             if self._fused_plan is not None:
                 with tracing.range("MetricCollection.fused_update"):
                     fused_done = self._fused_plan.try_run(*args, **kwargs)
+            # the multilabel plan: its leaders are of other kinds, so a
+            # collection runs at most one of the two
+            if self._fused_ml_plan is False:
+                self._fused_ml_plan = _FusedMultilabelUpdatePlan.build(self)
+            if self._fused_ml_plan is not None and not fused_done:
+                with tracing.range("MetricCollection.fused_ml_update"):
+                    fused_done = self._fused_ml_plan.try_run(*args, **kwargs)
             # run only each group's leader
             for members in self._groups.values():
                 leader = getattr(self, members[0])

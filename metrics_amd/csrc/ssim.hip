@@ -28,7 +28,11 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     // torch F.pad mode="reflect": -1 -> 1, n -> n-2 (requires pad < n)
     if (i < 0) i = -i;
     if (i >= n) i = 2 * n - 2 - i;
-    return i;
+    // A tile that reaches past a small image (n < TS) asks for patch cells more
+    // than the pad beyond the edge: 2n - 2 - i is negative there (n = 12,
+    // radius 5: down to -14). No output inside the image reads such a cell, but
+    // the load must stay inside the plane.
+    return min(max(i, 0), n - 1);
 }
 
 template <typename T>

@@ -104,7 +104,65 @@ def mc_step(num_classes: int, ignore_index: Optional[int], t: McStepTensors, k: 
     return rec
 
 
+class MlStepTensors(NamedTuple):
+    """The tensor objects one fused multilabel step works on, by name. Every
+    optional group is None when absent."""
+
+    counts: Tensor  # (6*L,) int64 count scratch: the step fills it, the tail zeroes it
+    records: Tensor  # one uint8 per block of the step kernel
+    tp: Optional[Tensor] = None  # the four stat states, (L,) each
+    fp: Optional[Tensor] = None
+    tn: Optional[Tensor] = None
+    fn: Optional[Tensor] = None
+    confmat: Optional[Tensor] = None  # (L, 2, 2) state
+    correct: Optional[Tensor] = None  # the exact-match states, with rowbad
+    total: Optional[Tensor] = None
+    rowbad: Optional[Tensor] = None  # (>=N,) int32 mismatch words, zero between steps
+    thresholds: Optional[Tensor] = None  # the curve group: float32 thresholds,
+    hist: Optional[Tensor] = None  # the lazy (L, T+1, 2) histogram,
+    epoch_buf: Optional[Tensor] = None  # the device epoch E
+    region_flags: Optional[Tensor] = None  # and one uint8 per region, zero between steps
+
+
+class MlStep(ctypes.Structure):
+    """Mirror of ``MlStep`` in csrc/ml_step.h, field for field. ``_load`` holds
+    field names, order and size against the header."""
+
+    _fields_ = [
+        ("L", _LL), ("ignore_index", _LL), ("has_ignore", _LL), ("thr", _D),
+        ("counts", _U64), ("records", _U64),
+        ("tp", _U64), ("fp", _U64), ("tn", _U64), ("fn", _U64), ("confmat", _U64),
+        ("correct", _U64), ("total", _U64), ("rowbad", _U64),
+        ("T", _LL), ("thresholds", _U64), ("uniform", _LL), ("t0", _D), ("inv_step", _D),
+        ("hist", _U64), ("epoch_buf", _U64), ("region_flags", _U64), ("region_cap", _LL),
+    ]
+
+
+_ML_STEP_P = ctypes.POINTER(MlStep)
+
+
+def ml_step(num_labels: int, ignore_index: Optional[int], threshold: float, t: MlStepTensors,
+            uniform: tuple = (0, 0.0, 1.0)) -> MlStep:
+    """The record of one multilabel step over ``num_labels`` labels and the
+    tensors ``t``, filled by name. The curve group is on iff ``t.thresholds`` is
+    given; ``uniform`` = its :func:`_uniform_params`. It holds bare addresses:
+    whoever keeps the record keeps ``t`` next to it."""
+    rec = MlStep(L=num_labels, ignore_index=ignore_index if ignore_index is not None else 0,
+                 has_ignore=ignore_index is not None, thr=float(threshold))
+    for name, x in zip(t._fields, t):
+        if x is not None:
+            setattr(rec, name, x.data_ptr())
+    if t.thresholds is not None:
+        rec.T = t.thresholds.shape[0]
+        rec.uniform, rec.t0, rec.inv_step = uniform
+        rec.region_cap = t.region_flags.shape[0]
+    return rec
+
+
 _SIGNATURES = {
+    "ma_ml_step": [_U64, _ML_STEP_P, _U64, _I, _U64, _LL],
+    "ma_ml_step_layout": [_LL, _LL, _I, ctypes.POINTER(_LL)],
+    "ma_ml_step_sizeof": [],
     "ma_mc_stat_logits": [_U64, _STEP_P, _U64, _I, _U64, _LL, _U64],
     "ma_mc_stat_topk_covers": [_LL],
     "ma_mc_stat_labels": [_U64, _STEP_P, _U64, _U64, _LL],
@@ -160,11 +218,24 @@ def _declare_argtypes(lib: ctypes.CDLL) -> None:
             f"McStep: the Python mirror {mirror} and csrc/mc_step.h {mc_step_native_fields(lib)} differ in"
             " field names, order or size; rebuild the library"
         )
+    lib.ma_ml_step_field_names.argtypes = []
+    lib.ma_ml_step_field_names.restype = ctypes.c_char_p
+    mirror = [name for name, _ in MlStep._fields_]
+    if ml_step_native_fields(lib) != mirror or lib.ma_ml_step_sizeof() != ctypes.sizeof(MlStep):
+        raise RuntimeError(
+            f"MlStep: the Python mirror {mirror} and csrc/ml_step.h {ml_step_native_fields(lib)} differ in"
+            " field names, order or size; rebuild the library"
+        )
 
 
 def mc_step_native_fields(lib: ctypes.CDLL) -> list:
     """The field names of the native ``McStep`` in declaration order."""
     return lib.ma_mc_step_field_names().decode().rstrip(",").split(",")
+
+
+def ml_step_native_fields(lib: ctypes.CDLL) -> list:
+    """The field names of the native ``MlStep`` in declaration order."""
+    return lib.ma_ml_step_field_names().decode().rstrip(",").split(",")
 
 
 def hip_available() -> bool:
@@ -1459,6 +1530,144 @@ def mc_onepass_update(
     # the suffix/confmat materialization waits for the first state read
     curve.__dict__["_hip_lazy_meta"] = (C, T, 1)
     curve.__dict__["_lazy_dirty"] = True
+    return True
+
+
+# Fused multilabel step (csrc/ml_step.hip). METRICS_AMD_FUSE_MULTILABEL=0 keeps
+# every leader of a multilabel collection on its own update path, exactly as
+# before (A/B lever, escape hatch and the oracle of the tests). Read when a
+# collection builds its plan.
+FUSE_MULTILABEL_ENV = "METRICS_AMD_FUSE_MULTILABEL"
+
+# Largest threshold count with which the curve leader rides the fused step: the
+# step kernel keeps a private histogram of one label chunk in LDS,
+# [CW][T+1][2] u32 plus the T float thresholds, next to 2048 bytes of static
+# LDS (block counters), against the 160 KiB of a gfx950 workgroup. The
+# narrowest chunk is CW = 16 labels: 16*(T+1)*8 + 4*T + 2048 <= 163840, i.e.
+# 132*T <= 161664 (ML_LDS_BYTES / ML_LDS_STATIC in csrc/ml_step.hip). Above it
+# the curve leader updates on its own and the other leaders still fuse.
+ML_STEP_MAX_T = (160 * 1024 - 2048 - 128) // 132  # 1224
+
+_ML_LAYOUT_CACHE: dict = {}
+
+
+class _MlStepRecord:
+    """A step record with the tensor objects whose addresses it holds, kept in
+    the ``__dict__`` of a leader. A copy or pickle of the leader gets None and
+    builds its own, as with :class:`_NativePlan`."""
+
+    __slots__ = ("tensors", "scalars", "rec")
+
+    def __init__(self, tensors, scalars, rec):
+        self.tensors, self.scalars, self.rec = tensors, scalars, rec
+
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (type(None), ())
+
+
+def fuse_multilabel_enabled() -> bool:
+    return os.environ.get(FUSE_MULTILABEL_ENV, "1") != "0"
+
+
+def ml_step_layout(num_labels: int, rows: int, num_thresholds: int) -> Optional[tuple]:
+    """(region flag bytes, record bytes, chunk width, rows per region, step
+    blocks, tail blocks) of a fused multilabel step, None where the kernels do
+    not cover the shape. ``num_thresholds`` 0: no curve leader. Host only."""
+    key = (num_labels, rows, num_thresholds)
+    if key not in _ML_LAYOUT_CACHE:
+        out = (_LL * 6)()
+        rc = _lib().ma_ml_step_layout(num_labels, rows, num_thresholds, out)
+        if len(_ML_LAYOUT_CACHE) > 256:
+            _ML_LAYOUT_CACHE.clear()
+        _ML_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _ML_LAYOUT_CACHE[key]
+
+
+def ml_step_update(
+    preds: Tensor, target: Tensor, num_labels: int, ignore_index: Optional[int], threshold: float,
+    stat=None, confmat=None, exact=None, curve=None,
+) -> bool:
+    """The whole step of a fused multilabel collection in ONE native call of two
+    launches that reads the (N, L) fp32 / bf16 ``preds`` and the int64
+    ``target`` once: per-label stat counts into the ``stat`` leader's
+    tp/fp/tn/fn, [[tn, fp], [fn, tp]] into the ``confmat`` leader's state, the
+    exact-match counts into the ``exact`` leader's correct/total, and the
+    threshold-curve histogram into the ``curve`` leader's lazy buffer (absent
+    leaders are None). Every buffer lives in the ``__dict__`` of the leader it
+    serves (:func:`owner_buffer`); no allocation, fill or host sync in steady
+    state. Both inputs must be contiguous.
+
+    Returns False without launching anything where the kernels do not cover
+    the shape: the caller lets every leader update on its own.
+    """
+    lib = _lib()
+    dt = _dtype_code(preds)
+    N, L = preds.shape
+    dev = preds.device
+    base = stat if stat is not None else confmat if confmat is not None else exact if exact is not None else curve
+    thr, T = None, 0
+    if curve is not None:
+        src = curve.thresholds
+        hit = curve.__dict__.get("_hip_ml_thr")
+        if hit is not None and hit[0] is src:
+            thr = hit[1]
+        else:
+            thr = src.contiguous().float()
+            curve.__dict__["_hip_ml_thr"] = (src, thr)
+        T = thr.numel()
+    lay = ml_step_layout(L, N, T)
+    if lay is None:
+        return False
+    tensors = MlStepTensors(
+        counts=owner_buffer(base, "_hip_ml_counts", (6 * L,), torch.long, dev),
+        records=owner_buffer(base, "_hip_ml_records", (lay[1],), torch.uint8, dev),
+        tp=stat.tp if stat is not None else None,
+        fp=stat.fp if stat is not None else None,
+        tn=stat.tn if stat is not None else None,
+        fn=stat.fn if stat is not None else None,
+        confmat=confmat.confmat if confmat is not None else None,
+        correct=exact.correct if exact is not None else None,
+        total=exact.total if exact is not None else None,
+        rowbad=owner_buffer(exact, "_hip_ml_rowbad", (max(N, 1),), torch.int32, dev, grow=True)
+        if exact is not None else None,
+    )
+    if curve is not None:
+        tensors = tensors._replace(
+            thresholds=thr,
+            hist=_pooled_hist(L, T, dev, curve),
+            epoch_buf=_epoch_buf(dev, curve),
+            region_flags=owner_buffer(curve, "_hip_ml_region_flags", (max(lay[0], 1),), torch.uint8, dev, grow=True),
+        )
+    # the record holds the addresses of everything that stays the same from
+    # step to step; reset() and a move to another device replace state tensors
+    # and the next step rebuilds it (the identity rule of _NativePlan.fits)
+    scalars = (L, ignore_index, float(threshold), T)
+    kept = base.__dict__.get("_hip_ml_rec")
+    if kept is not None and kept.scalars == scalars and all(map(operator.is_, kept.tensors, tensors)):
+        rec = kept.rec
+    else:
+        for name in ("tp", "fp", "tn", "fn", "confmat", "correct", "total"):
+            x = getattr(tensors, name)
+            if x is not None and not (x.is_contiguous() and x.dtype == torch.long and x.device == dev):
+                return False
+        rec = ml_step(L, ignore_index, threshold, tensors, _uniform_params(thr) if curve is not None else (0, 0.0, 1.0))
+        base.__dict__["_hip_ml_rec"] = _MlStepRecord(tensors, scalars, rec)
+    rc = lib.ma_ml_step(_stream(), rec, preds.data_ptr(), dt, target.data_ptr(), N)
+    if rc == -103:
+        return False  # nothing was launched
+    _check(rc, "ma_ml_step")
+    for name in ("tp", "fp", "tn", "fn", "confmat", "correct", "total"):
+        x = getattr(tensors, name)
+        if x is not None:
+            _mark_kernel_mutated(x)
+    if curve is not None:
+        # same lazy protocol as curve_hist_into_confmat: the histogram
+        # accumulates, the suffix/confmat materialization waits for a state read
+        curve.__dict__["_hip_lazy_meta"] = (L, T, 1)
+        curve.__dict__["_lazy_dirty"] = True
     return True
 
 
