@@ -487,7 +487,8 @@ class _FusedMulticlassComputePlan:
                 return False
             curve.__dict__["_lazy_dirty"] = False  # the step is the flush
             flush = True
-        out, auc = native.step(flush)
+        # a histogram the one-pass step left in pending format is completed by the same call
+        out, auc = native.step(flush, _hip.take_b0_pending(curve) if flush else None)
         self.steps += 1
         vals = out.unbind(0)
         for m, kind, spec, slot in todo:
@@ -548,9 +549,12 @@ class MetricCollection(ModuleDict):
     def update(self, *args: Any, **kwargs: Any) -> None:
         """Call update on every metric (or only group leaders once groups are formed)."""
         if self._groups_checked:
-            # invalidate cached compute results on ALL members
-            for k in self.keys(keep_base=True):
-                getattr(self, str(k))._computed = None
+            # invalidate cached compute results on ALL members; straight from
+            # the module dict: a Module attribute lookup per member and step
+            # costs more than everything else in this loop
+            modules = self._modules
+            for m in modules.values():
+                m._computed = None
             if self._fused_plan is False:
                 self._fused_plan = _FusedMulticlassUpdatePlan.build(self)
             fused_done: tuple = ()
@@ -565,11 +569,12 @@ class MetricCollection(ModuleDict):
                 with tracing.range("MetricCollection.fused_ml_update"):
                     fused_done = self._fused_ml_plan.try_run(*args, **kwargs)
             # run only each group's leader
+            # identity check: Metric.__eq__ is the compositional operator
+            # (returns a CompositionalMetric, which is always truthy)
+            done_ids = set(map(id, fused_done)) if fused_done else ()
             for members in self._groups.values():
-                leader = getattr(self, members[0])
-                # identity check: Metric.__eq__ is the compositional operator
-                # (returns a CompositionalMetric, which is always truthy)
-                if any(leader is m for m in fused_done):
+                leader = modules[members[0]]
+                if id(leader) in done_ids:
                     leader._update_count += 1
                     continue
                 leader.update(*args, **leader._filter_kwargs(**kwargs))

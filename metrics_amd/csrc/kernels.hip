@@ -733,6 +733,42 @@ __global__ void k_curve_suffix_tiled(
     if (E && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&E[1], 1u);
 }
 
+// Pay what a histogram in "pending b0" format still owes (mc_onepass.hip): the
+// one-pass step leaves out every element of bucket b0 = bucket_of(0.0f) of the
+// rows it bins from registers and keeps, per class and since the last flush,
+// P[c] = binned rows whose target is c and R[c] = binned rows. Class c got one
+// element per such row, label 1 for P[c] of them, so
+//     hist[c][b0][1] += P[c]          - sum_j hist[c][j][1]
+//     hist[c][b0][0] += (R[c] - P[c]) - sum_j hist[c][j][0]
+// completes it exactly. One wave per class: lane l sums the words l, l + 64,
+// ... of the class row (coalesced; 64 is even, so a lane keeps to one label),
+// the lanes of a label are added up, lane 0 stores both. Plain stores: the
+// kernel runs between a step and the suffix kernel, alone on the histogram.
+// P and R are zeroed here: the histogram no longer owes anything.
+__global__ void __launch_bounds__(256) k_curve_resolve_pending(
+    unsigned long long* __restrict__ hist /* (C, T+1, 2) */, ll C, int T,
+    const float* __restrict__ thresholds, unsigned long long* __restrict__ P,
+    unsigned long long* __restrict__ R) {
+    typedef unsigned long long ull;
+    const int lane = threadIdx.x & 63;
+    const ll c = (ll)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (c >= C) return;  // whole waves leave: c is wave-uniform
+    const int row = (T + 1) * 2;
+    ull* h = hist + c * (ll)row;
+    ull sum = 0;
+    for (int j = lane; j < row; j += 64) sum += h[j];
+    for (int off = 32; off >= 2; off >>= 1) sum += __shfl_down(sum, off);
+    const ull sum1 = __shfl(sum, 1);  // label 1; lane 0 holds label 0
+    if (lane == 0) {
+        const ull p = P[c], r = R[c];
+        const int b0 = bucket_of(0.0f, thresholds, T);
+        h[b0 * 2 + 0] += (r - p) - sum;
+        h[b0 * 2 + 1] += p - sum1;
+        P[c] = 0;
+        R[c] = 0;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // fused (C,C) confusion-matrix scalar computes: MCC + unweighted Cohen kappa +
 // macro Jaccard in TWO launches. The eager torch chains emit ~25 small
@@ -1256,9 +1292,29 @@ int ma_multiclass_curve_hist(uintptr_t stream, uintptr_t probs, int dtype, uintp
     return (int)hipGetLastError();
 }
 
+// Complete a (C, T+1, 2) histogram in pending-b0 format in place
+// (k_curve_resolve_pending). pending = [P: C][R: C] u64, the head of the
+// one-pass curve scratch; 0 = the histogram owes nothing: no launch.
+int ma_curve_resolve_pending(uintptr_t stream, uintptr_t hist, ll C, int T, uintptr_t thresholds,
+                             uintptr_t pending) {
+    if (!pending) return 0;
+    if (!hist || !thresholds || C <= 0 || T < 1) return -103;
+    unsigned long long* pr = (unsigned long long*)pending;
+    k_curve_resolve_pending<<<(int)((C + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+        (unsigned long long*)hist, C, T, (const float*)thresholds, pr, pr + C);
+    return (int)hipGetLastError();
+}
+
+// pending / thresholds: see ma_curve_resolve_pending, which then runs in front
+// of the suffix kernel (both 0 for a histogram that owes nothing)
 int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int transposed,
-                    int zero_hist, uintptr_t epoch_buf, uintptr_t confmat) {
+                    int zero_hist, uintptr_t epoch_buf, uintptr_t confmat, uintptr_t pending,
+                    uintptr_t thresholds) {
     hipStream_t s = (hipStream_t)stream;
+    if (pending) {
+        const int rc = ma_curve_resolve_pending(stream, hist, outer, T, thresholds, pending);
+        if (rc != 0) return rc;
+    }
     if (transposed) {
         static int ctile_sel = 0;
         if (ctile_sel == 0) {

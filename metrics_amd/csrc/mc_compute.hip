@@ -4,7 +4,9 @@
 // A MetricCollection.compute() used to enter one Python wrapper per metric,
 // each with its own cache lookup, output allocation and launch: about twenty
 // launches for ~85 us of kernels inside a ~290 us call (profiles/README.md,
-// "Collection compute plan"). One step of the plan makes at most three:
+// "Collection compute plan"). One step of the plan makes at most three, and
+// one more in front of them when the histogram is in pending-b0 format
+// (k_curve_resolve_pending, kernels.hip):
 //
 //   1. k_curve_flush_auc<CTILE>   lazy curve flush (histogram -> (T, C, 2, 2)
 //                                 state) and, from the tile still in LDS,
@@ -24,7 +26,7 @@
 //   ma_compute_plan_create(C, T, tp, fp, tn, fn, confmat, cm_scratch, correct,
 //                          total, hist, curve_state, epoch_buf, params,
 //                          n_formulas, zero_division, auc_stride, &handle)
-//   ma_compute_plan_step(handle, stream, flags, out, auc_out)
+//   ma_compute_plan_step(handle, stream, flags, out, auc_out, pending, thresholds)
 //   ma_compute_plan_destroy(handle)
 
 #include <hip/hip_runtime.h>
@@ -39,7 +41,10 @@ typedef unsigned long long ull;
 // kernels.hip
 extern "C" int ma_confmat_moments(uintptr_t stream, uintptr_t cm, ll C, uintptr_t scratch);
 extern "C" int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int transposed,
-                               int zero_hist, uintptr_t epoch_buf, uintptr_t confmat);
+                               int zero_hist, uintptr_t epoch_buf, uintptr_t confmat,
+                               uintptr_t pending, uintptr_t thresholds);
+extern "C" int ma_curve_resolve_pending(uintptr_t stream, uintptr_t hist, ll C, int T,
+                                        uintptr_t thresholds, uintptr_t pending);
 extern "C" int ma_curve_auc_from_confmat(uintptr_t stream, uintptr_t confmat, int T, ll C,
                                          int mode, uintptr_t out, uintptr_t weights);
 
@@ -136,10 +141,16 @@ static int compute_ctile() {
 }
 
 static int compute_step(const ComputePlan& p, hipStream_t s, int flags, float* out,
-                        float* auc_out) {
+                        float* auc_out, uintptr_t pending, uintptr_t thresholds) {
     const int flush = (flags & MA_COMPUTE_FLUSH) ? 1 : 0;
+    if (pending && !(flush && p.curve_state)) return -103;  // owed counts are paid by a flush only
     if (p.curve_state) {
         if (!auc_out || (flush && !p.hist)) return -103;
+        if (pending) {
+            const int rc = ma_curve_resolve_pending((uintptr_t)s, (uintptr_t)p.hist, p.C, p.T,
+                                                    thresholds, pending);
+            if (rc != 0) return rc;
+        }
         if (p.curve_lds) {
             const int grid = (int)((p.C + p.ctile - 1) / p.ctile);
             if (p.ctile == 2)
@@ -159,7 +170,7 @@ static int compute_step(const ComputePlan& p, hipStream_t s, int flags, float* o
             int rc = 0;
             if (flush)
                 rc = ma_curve_suffix((uintptr_t)s, (uintptr_t)p.hist, p.C, p.T, 1, 1,
-                                     (uintptr_t)p.epoch_buf, (uintptr_t)p.curve_state);
+                                     (uintptr_t)p.epoch_buf, (uintptr_t)p.curve_state, 0, 0);
             for (int mode = 0; mode < 2 && rc == 0; mode++)
                 rc = ma_curve_auc_from_confmat(
                     (uintptr_t)s, (uintptr_t)p.curve_state, p.T, p.C, mode,
@@ -215,11 +226,13 @@ int ma_compute_plan_create(ll C, int T, uintptr_t tp, uintptr_t fp, uintptr_t tn
     return 0;
 }
 
+// pending / thresholds: the curve histogram is in pending-b0 format (see
+// ma_curve_resolve_pending); both 0 otherwise. Only with MA_COMPUTE_FLUSH.
 int ma_compute_plan_step(uintptr_t handle, uintptr_t stream, int flags, uintptr_t out,
-                         uintptr_t auc_out) {
+                         uintptr_t auc_out, uintptr_t pending, uintptr_t thresholds) {
     if (!handle) return -103;
     return compute_step(*(const ComputePlan*)handle, (hipStream_t)stream, flags, (float*)out,
-                        (float*)auc_out);
+                        (float*)auc_out, pending, thresholds);
 }
 
 void ma_compute_plan_destroy(uintptr_t handle) { delete (ComputePlan*)handle; }

@@ -44,17 +44,30 @@
 // were deferred all blocks grid-stride over the (class-chunk, 256-row) tiles
 // of the deferred pass (curve_hist_tile, shared with kernels.hip).
 //
-// COMPLEMENT IDENTITY: after softmax almost every element of a row falls into
-// one bucket b0 = bucket_of(+0.0f). Those elements issue no atomic at all.
-// Per class the kernel counts P[c] (binned rows whose target is c) and
-// N1[c]/N0[c] (elements binned OUTSIDE b0, by label); the epilogue adds
-//     hist[c][b0][1] += P[c] - N1[c]
-//     hist[c][b0][0] += (n_binned - P[c]) - N0[c]
-// which is an exact integer identity (class total minus the rest), so the
-// histogram equals the two-kernel result bit for bit.
+// PENDING-b0 HISTOGRAM: after softmax almost every element of a row falls into
+// one bucket b0 = bucket_of(+0.0f). Those elements issue no atomic at all, and
+// nothing counts them per step either: the histogram is lazy (nobody reads it
+// between two flushes), so between flushes it may lack exactly the b0 elements
+// of the rows k_mc_onepass binned from registers. Two per-class u64 vectors in
+// the curve scratch, cumulative since the last flush, carry what is missing:
+//     P[c]  non-ignored rows binned so far (either kernel) whose target is c
+//     R[c]  non-ignored rows binned so far (the same number in every slot;
+//           per class so that no word is shared between blocks)
+// Every such row adds one element to class c, label 1 if its target is c, so at
+// any kernel boundary after a step
+//     P[c]          - sum_j hist[c][j][1]   is still owed to hist[c][b0][1]
+//     (R[c] - P[c]) - sum_j hist[c][j][0]   is still owed to hist[c][b0][0]
+// exact integer identities (class total minus what is there). The flush
+// (k_curve_resolve_pending in kernels.hip, in front of the suffix kernel) pays
+// both and zeroes P and R, so the flushed histogram equals the two-kernel
+// result bit for bit. Per step this leaves one atomic per element outside b0
+// and one per row, where a per-step complement needed a second per element.
+// P is not tp + fn of the stat scratch: count_row rejects a row whose argmax is
+// out of range (an all-NaN row), yet that row is binned.
 //
 // A done row (binned or ignored) is marked rowinv[row] = -rinv; a true rinv is
-// always > 0, so the sign is free.
+// always > 0, so the sign is free. A rinv that is not > 0 (NaN, 0) is marked
+// -1: the tail only tests the sign of a done row.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -70,18 +83,14 @@
 typedef long long ll;
 typedef unsigned long long ull;
 
-// curve scratch layout (u64): [P: C][N1: C][N0: NCOPY x C][records: 2 x GRID_MAX][flags: GRID_MAX / 8]
-// N0[c] takes ~150 increments per class and step at the bench shape; on one
-// address they serialise (measured: 10 us of the kernel). NCOPY copies, picked
-// by block index (consecutive blocks land on different XCDs), spread them; the
-// epilogue sums the copies.
+// curve scratch layout (u64): [P: C][R: C][records: 2 x GRID_MAX][flags: GRID_MAX / 8]
+// P and R: see PENDING-b0 above; zeroed by the flush, never by a step.
 // records: one uint4 per k_mc_onepass block, {valid, binned, deferred | outside
 // << 31, correct}. Never zeroed: every launched block overwrites its own record
 // every step and the tail kernel reads exactly `grid` of them. The region
-// starts 80*C bytes into the 16-byte aligned scratch, so it is 16-byte aligned.
-#define ONEPASS_NCOPY 8
+// starts 16*C bytes into the 16-byte aligned scratch, so it is 16-byte aligned.
 #define ONEPASS_GRID_MAX 1024  // records the scratch holds = cap of MA_ONEPASS_GRID
-#define ONEPASS_REC_OFF(C) ((2 + ONEPASS_NCOPY) * (C))
+#define ONEPASS_REC_OFF(C) (2 * (C))
 // flags: one byte per k_mc_onepass block behind the records, bit 0 = the block
 // deferred a row, bit 1 = its "outside" bit: all a tail block without an
 // epilogue slice needs, 1 KB instead of the 16 KB of records. Overwritten every
@@ -99,7 +108,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     int has_ignore, ull* __restrict__ tp, ull* __restrict__ fp, ull* __restrict__ fn,
     ull* __restrict__ confmat, float* __restrict__ rowmax, float* __restrict__ rowinv,
     const float* __restrict__ thresholds, int T, int uniform, float t0, float inv_step,
-    ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cs /* [P|N1|N0 copies] */,
+    ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cP /* C, cumulative */,
     uint4* __restrict__ records /* gridDim.x */, unsigned char* __restrict__ flags /* gridDim.x */,
     int topk, ull* __restrict__ tp2, ull* __restrict__ fp2, ull* __restrict__ fn2 /* TOPK only */) {
     constexpr int EPV = 16 / sizeof(T_);  // elements per 16-byte vector
@@ -113,9 +122,6 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     const int waves_per_block = blockDim.x / WAVE;
     const ll row_stride = (ll)gridDim.x * waves_per_block;
     const int nvec = (int)(C / EPV);  // C <= 4096 here: 32-bit class indices
-    ull* __restrict__ cP = cs;
-    ull* __restrict__ cN1 = cs + C;
-    ull* __restrict__ cN0 = cs + (2 + (blockIdx.x & (ONEPASS_NCOPY - 1))) * C;
     unsigned int outside = 0;
     unsigned int my_valid = 0, my_binned = 0, my_deferred = 0, my_correct = 0;
 
@@ -204,7 +210,10 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
                 if constexpr (TOPK) count_row_topk(t, p, rank, topk, tp2, fp2, fn2);
             }
             rowmax[row] = rmax;
-            rowinv[row] = (bin_now || ignored) ? -rinv : rinv;
+            // the done mark must compare < 0 whatever rinv is: a row with a NaN
+            // next to an element outside [0,1] has rinv = NaN, an infinite sum
+            // gives 0, and the tail would bin such a row a second time
+            rowinv[row] = (bin_now || ignored) ? (rinv > 0.0f ? -rinv : -1.0f) : rinv;
             if (bin_now) {
                 my_binned++;
                 if (t >= 0 && t < C) atomicAdd(&cP[t], 1ULL);
@@ -213,7 +222,7 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             }
         }
 
-        // ---- phase B: bin from registers; bucket b0 is filled by the epilogue ----
+        // ---- phase B: bin from registers; bucket b0 stays pending until the flush ----
         if (bin_now) {
             // out-of-range targets bin with every label 0, like the two-kernel path
             const int tc = (t >= 0 && t < C) ? (int)t : -1;
@@ -224,7 +233,6 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
                 if (j != b0) {
                     const int label = (tc == c) ? 1 : 0;
                     atomicAdd(&hist[(ull)c * (T + 1) * 2 + j * 2 + label], 1ULL);
-                    atomicAdd(label ? &cN1[c] : &cN0[c], 1ULL);
                 }
             };
             // EXACT pre-filter in the logit domain. p = expf(d) * rinv with
@@ -311,14 +319,17 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
 //      16-byte records (<= 16 KB) for valid / binned / correct: with 4096
 //      blocks that is 4 MB of L2 reads per step in place of 64 MB;
 //  (b) applies the epilogue for class blockIdx.x*256 + threadIdx.x, if there
-//      is one: k_apply_stat_exact's stat deltas plus the complement fill of
-//      bucket b0. Each slot of both scratches is read and zeroed by the same
-//      thread. The b0 fill is an atomicAdd because in (c) other blocks of this
-//      launch add to the same histogram words. Block 0 also applies the
-//      exact-match scalars and closes the device epoch — at once, since no
+//      is one: k_apply_stat_exact's stat deltas, and R[class] += the step's
+//      binned + deferred rows (a plain add: the thread is the only writer of
+//      its slot). Each slot of the stat scratches is read and zeroed by the
+//      same thread. No histogram word is touched here. Block 0 also applies
+//      the exact-match scalars and closes the device epoch — at once, since no
 //      block of this kernel reads E: the softmax decision is `outside`;
 //  (c) returns if nothing was deferred (every logits input), else grid-strides
-//      over the (class-chunk, 256-row) tiles of the deferred pass.
+//      over the (class-chunk, 256-row) tiles of the deferred pass. A deferred
+//      row adds all its elements, b0 included; the chunk-0 tile of each row
+//      tile adds 1 to P[target] for every row the tiles bin (the tile's own
+//      condition), so each such row is counted exactly once.
 // Nothing written by one block is read by another; there is no ticket, spin
 // or grid-wide wait.
 template <typename T_, bool TOPK>
@@ -327,7 +338,7 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     int grid /* blocks k_mc_onepass ran with */,
     ull* __restrict__ scratch /* 3*C + 1 */, ll C, ll B, ll* __restrict__ tp, ll* __restrict__ fp,
     ll* __restrict__ tn, ll* __restrict__ fn, ll* __restrict__ correct /* nullable */,
-    ll* __restrict__ total, unsigned int* __restrict__ E, ull* __restrict__ cs /* [P|N1|N0 copies] */,
+    ll* __restrict__ total, unsigned int* __restrict__ E, ull* __restrict__ cs /* [P: C][R: C] */,
     const float* __restrict__ thresholds, int T, ull* __restrict__ hist /* (C, T+1, 2) */,
     const T_* __restrict__ probs, const ll* __restrict__ target, ll ignore_index, int has_ignore,
     int uniform, float t0, float inv_step, int c_chunk, const float* __restrict__ rowmax,
@@ -343,12 +354,13 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     // ---- (a) the batch-global flags; the counts where the epilogue needs them ----
     unsigned int fl = 0;
     for (int i = threadIdx.x; i < grid; i += blockDim.x) fl |= flags[i];
-    unsigned int r_valid = 0, r_binned = 0, r_correct = 0;
+    // r_rows: rows this step bins, here or in k_mc_onepass (B < 2^31: no overflow)
+    unsigned int r_valid = 0, r_rows = 0, r_correct = 0;
     if (has_slice) {
         for (int i = threadIdx.x; i < grid; i += blockDim.x) {
             const uint4 r = records[i];
             r_valid += r.x;
-            r_binned += r.y;
+            r_rows += r.y + (r.z & 0x7fffffffu);
             r_correct += r.w;
         }
     }
@@ -356,21 +368,21 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
     if (has_slice) {
         for (int off = WAVE / 2; off > 0; off >>= 1) {
             r_valid += __shfl_down(r_valid, off);
-            r_binned += __shfl_down(r_binned, off);
+            r_rows += __shfl_down(r_rows, off);
             r_correct += __shfl_down(r_correct, off);
         }
     }
     const unsigned int wave_fl = (__ballot(fl & 1u) != 0ULL ? 1u : 0u) | (__ballot(fl & 2u) != 0ULL ? 2u : 0u);
     if (lane == 0) {
-        wsum[wave][0] = r_valid; wsum[wave][1] = r_binned; wsum[wave][2] = r_correct;
+        wsum[wave][0] = r_valid; wsum[wave][1] = r_rows; wsum[wave][2] = r_correct;
         wsum[wave][3] = wave_fl;
     }
     __syncthreads();
-    ll valid = 0, binned = 0;
+    ll valid = 0, rows = 0;
     unsigned int ncorrect = 0, all_fl = 0;
 #pragma unroll
     for (int w = 0; w < 256 / WAVE; w++) {
-        valid += wsum[w][0]; binned += wsum[w][1]; ncorrect += wsum[w][2]; all_fl |= wsum[w][3];
+        valid += wsum[w][0]; rows += wsum[w][1]; ncorrect += wsum[w][2]; all_fl |= wsum[w][3];
     }
     const bool deferred = (all_fl & 1u) != 0;  // some row waits for this kernel
     const unsigned int outside = all_fl >> 1;
@@ -381,22 +393,7 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
         apply_stat_class(scratch, C, i, valid, tp, fp, tn, fn);
         // the top-k slot: the same valid, its own scratch and states
         if constexpr (TOPK) apply_stat_class(scratch2, C, i, valid, tp2, fp2, tn2, fn2);
-        if (binned) {  // no row binned => the three counters are already zero
-            const int b0 = bucket_of(0.0f, sthr_t, T);
-            const ll P = (ll)cs[i];
-            const ll N1 = (ll)cs[C + i];
-            ll N0 = 0;
-#pragma unroll
-            for (int q = 0; q < ONEPASS_NCOPY; q++) {
-                N0 += (ll)cs[(2 + q) * C + i];
-                cs[(2 + q) * C + i] = 0;
-            }
-            cs[i] = 0;
-            cs[C + i] = 0;
-            ull* h = hist + ((ull)i * (T + 1) + b0) * 2;
-            atomicAdd(&h[1], (ull)(P - N1));
-            atomicAdd(&h[0], (ull)((binned - P) - N0));
-        }
+        if (rows) cs[C + i] += (ull)rows;  // R[i]
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (correct) {
@@ -436,6 +433,21 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
         curve_hist_tile<T_>(probs, target, B, C, sthr_t, T, ignore_index, has_ignore, /*mode=*/0,
                             uniform, t0, inv_step, c_lo, c_hi, ry * 256, norm, rowmax, rowinv,
                             /*skip_done=*/true, hist);
+        // P[target] of the rows the tiles of this row tile bin, under
+        // curve_hist_tile's own condition (in range, not ignored, not marked
+        // done). Every (chunk, row tile) pair is walked exactly once, so the
+        // chunk-0 tile counts each of its 256 rows once; asking every tile
+        // whether its chunk holds the target re-read target and rowinv for
+        // each of the C/c_chunk chunks (measured: +2 us on all-deferred input)
+        if (chunk == 0) {
+            const ll prow = ry * 256 + threadIdx.x;
+            if (prow < B) {
+                const ll pt = target[prow];
+                if (pt >= 0 && pt < C && !(has_ignore && pt == ignore_index) &&
+                    !(rowinv[prow] < 0.0f))
+                    atomicAdd(&cs[pt], 1ULL);
+            }
+        }
     }
 }
 
@@ -601,9 +613,11 @@ extern "C" {
 // block (its valid slot is not used here), the stat states, the row statistics
 // and the epoch buffer; confmat, correct/total and the top-k slot (k > 0: every
 // step also counts and applies it) are optional. cscratch = curve scratch
-// [P|N1|N0 copies|records] (ma_mc_onepass_scratch_words(C) u64). The counters
-// of all blocks are zero before the first step and zero again after every
-// tail, the records need no zeroing.
+// [P|R|records|flags] (ma_mc_onepass_scratch_words(C) u64). P and R are zero
+// before the first step and grow until the flush zeroes them again
+// (k_curve_resolve_pending); records and flags need no zeroing. While P or R
+// is nonzero, hist is in pending format and must go through that flush before
+// anything else reads or adds to it.
 int ma_onepass_plan_create(const McStep* st, int dtype, uintptr_t thresholds, int T, int uniform,
                            float t0, float inv_step, uintptr_t hist, uintptr_t cscratch,
                            unsigned long long* handle) {

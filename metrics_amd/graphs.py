@@ -69,6 +69,11 @@ class GraphedUpdate:
             for _ in range(warmup):
                 target.update(*self._static)
         torch.cuda.current_stream().wait_stream(side)
+        # the warmup may have left a curve histogram with another writer's rows
+        # than the captured update will add (one-pass step or not): flush here,
+        # so that no writer switch has to be decided inside the captured region
+        for m in self._metrics:
+            m._maybe_flush_lazy()
         torch.cuda.synchronize()
 
         # compute-group leaders are independent (disjoint states, read-only
@@ -92,6 +97,10 @@ class GraphedUpdate:
             else:
                 target.update(*self._static)
 
+        # the metrics whose captured update is the one-pass step: every replay
+        # leaves their histogram in pending-b0 format (ops/_hip.take_b0_pending)
+        self._b0_pending = tuple(m for m in self._metrics if m.__dict__.get("_hip_b0_pending"))
+
         # capture records but does not execute: only the warmup polluted the
         # states — restore defaults IN PLACE (the graph holds state pointers)
         self._reset_states_inplace()
@@ -110,6 +119,7 @@ class GraphedUpdate:
             if buf is not None:
                 buf.zero_()
             m.__dict__["_lazy_dirty"] = False
+            m._discard_lazy()  # the pending-b0 row counts go with the histogram
 
     def reset_states(self) -> None:
         """In-place equivalent of ``target.reset()`` (``reset()`` allocates new
@@ -123,6 +133,13 @@ class GraphedUpdate:
         """Copy the batch into the static buffers and replay the captured graph."""
         for buf, a in zip(self._static, args):
             buf.copy_(a, non_blocking=True)
+        # the writer-switch rules of the pending-b0 format, decided here and not
+        # in the graph: the captured writer must find the histogram in its own
+        # format (an update outside the graph may have been the last writer)
+        for m in self._metrics:
+            own = m.__dict__
+            if "_hip_lazy_meta" in own and any(m is p for p in self._b0_pending) != bool(own.get("_hip_b0_pending")):
+                m._maybe_flush_lazy()
         self.graph.replay()
         for m in self._metrics:
             m._update_count += 1
@@ -131,6 +148,8 @@ class GraphedUpdate:
             # so the next state read materializes the accumulated histogram
             if "_hip_lazy_meta" in m.__dict__:
                 m.__dict__["_lazy_dirty"] = True
+        for m in self._b0_pending:
+            m.__dict__["_hip_b0_pending"] = True
         # copy-on-access (items()/values()) de-aliases compute-group members;
         # re-establish the state refs so compute() sees the leaders' states
         t = self.target

@@ -293,6 +293,20 @@ class Metric(Module, ABC):
             self.__dict__["_lazy_dirty"] = False
             self._lazy_flush()
 
+    def _discard_lazy(self) -> None:
+        """Drop what the lazy curve path accumulated since the last flush: the
+        histogram and, if the one-pass step left it in pending format, the row
+        counts that go with it (``_hip.take_b0_pending``)."""
+        own = self.__dict__
+        if own.get("_lazy_dirty"):
+            own["_lazy_dirty"] = False
+            buf = own.get("_hip_hist_buf")
+            if buf is not None:
+                buf.zero_()
+        if own.get("_hip_b0_pending"):
+            own["_hip_b0_pending"] = False
+            own["_hip_onepass_scratch"].zero_()
+
     def _compute_plan_spec(self) -> Optional[tuple]:
         """What ``compute()`` evaluates, declared to the collection compute plan
         (``collections._FusedMulticlassComputePlan``), or None if the metric
@@ -649,11 +663,7 @@ class Metric(Module, ABC):
 
     def reset(self) -> None:
         """Reset all metric states to their defaults."""
-        if self.__dict__.get("_lazy_dirty"):
-            self.__dict__["_lazy_dirty"] = False
-            buf = self.__dict__.get("_hip_hist_buf")
-            if buf is not None:
-                buf.zero_()
+        self._discard_lazy()
         self._update_count = 0
         self._forward_cache = None
         self._computed = None
@@ -818,11 +828,7 @@ class Metric(Module, ABC):
         unexpected_keys: List[str],
         error_msgs: List[str],
     ) -> None:
-        if self.__dict__.get("_lazy_dirty"):
-            self.__dict__["_lazy_dirty"] = False
-            buf = self.__dict__.get("_hip_hist_buf")
-            if buf is not None:
-                buf.zero_()
+        self._discard_lazy()
         for key in self._defaults:
             name = prefix + key
             if name in state_dict:

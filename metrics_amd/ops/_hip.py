@@ -174,12 +174,13 @@ _SIGNATURES = {
     "ma_multilabel_stat": [_U64, _U64, _I, _U64, _LL, _LL, _F, _LL, _I, _U64, _U64],
     "ma_binary_curve_hist": [_U64, _U64, _I, _U64, _LL, _U64, _I, _LL, _I, _I, _F, _F, _I, _U64, _U64],
     "ma_multiclass_curve_hist": [_U64, _U64, _I, _U64, _LL, _LL, _U64, _I, _LL, _I, _I, _I, _F, _F, _I, _U64, _U64, _U64, _I, _I, _I, _U64],
-    "ma_curve_suffix": [_U64, _U64, _LL, _I, _I, _I, _U64, _U64],
+    "ma_curve_suffix": [_U64, _U64, _LL, _I, _I, _I, _U64, _U64, _U64, _U64],
+    "ma_curve_resolve_pending": [_U64, _U64, _LL, _I, _U64, _U64],
     "ma_curve_epoch_bump": [_U64, _U64],
     "ma_confmat_scalars": [_U64, _U64, _LL, _U64, ctypes.c_float, _U64],
     "ma_confmat_moments": [_U64, _U64, _LL, _U64],
     "ma_compute_plan_create": [_LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _F, _LL, ctypes.POINTER(ctypes.c_ulonglong)],
-    "ma_compute_plan_step": [_U64, _U64, _I, _U64, _U64],
+    "ma_compute_plan_step": [_U64, _U64, _I, _U64, _U64, _U64, _U64],
     "ma_linear_stat_multi": [_U64, _U64, _U64, _U64, _U64, _LL, _I, _U64, _U64],
     "ma_mc_onepass_nv": [_I, _LL, _I],
     "ma_mc_onepass_scratch_words": [_LL],
@@ -607,6 +608,8 @@ def binary_curve_confmat(
         0,
         0,
         confmat.data_ptr(),
+        0,
+        0,
     )
     _check(rc, "ma_curve_suffix")
     return confmat
@@ -662,6 +665,8 @@ def multiclass_curve_confmat(
         0,
         0,
         confmat.data_ptr(),
+        0,
+        0,
     )
     _check(rc, "ma_curve_suffix")
     return confmat
@@ -1062,6 +1067,8 @@ def curve_hist_into_confmat(
     the suffix kernel in-flight, so steady-state updates launch no fills.
     """
     lib = _lib()
+    if owner is not None:
+        flush_if_b0_pending(owner)  # the one-pass step wrote last: complete its histogram first
     thr = thresholds.contiguous().float()
     T = thr.numel()
     uni, t0, inv_step = _uniform_params(thr)
@@ -1166,6 +1173,8 @@ def curve_hist_into_confmat(
         1,  # re-zero the pooled hist in-flight
         _epoch_buf(dev, owner).data_ptr() if norm is not None else 0,
         confmat_state.data_ptr(),
+        0,
+        0,
     )
     _check(rc, "ma_curve_suffix")
 
@@ -1245,10 +1254,72 @@ def flush_curve_hist(owner) -> None:
     outer, T, transposed = meta
     confmat = owner.confmat
     assert confmat.is_contiguous() and confmat.device == buf.device
+    pending = take_b0_pending(owner)
     rc = _lib().ma_curve_suffix(
-        _stream(), buf.data_ptr(), outer, T, transposed, 1, 0, confmat.data_ptr()
+        _stream(), buf.data_ptr(), outer, T, transposed, 1, 0, confmat.data_ptr(),
+        pending[0].data_ptr() if pending else 0, pending[1].data_ptr() if pending else 0,
     )
     _check(rc, "ma_curve_suffix")
+
+
+# "Pending b0" protocol of the one-pass step (csrc/mc_onepass.hip). Between two
+# flushes the owner's lazy histogram may lack the elements of the bucket of 0.0;
+# the head of ``_hip_onepass_scratch`` ([P: C][R: C]) says how many. The owner's
+# ``_hip_b0_pending`` is True exactly while P or R may be nonzero, and then
+# ``_lazy_dirty`` is True as well. Rules, all decided on the host outside any
+# captured region:
+#   - every flush passes the scratch to the native flush, which pays what is
+#     owed in front of the suffix kernel and zeroes P and R (take_b0_pending);
+#   - a one-pass step on an owner that is dirty but not pending flushes first;
+#   - any other writer of the owner's histogram flushes first when the owner is
+#     pending (flush_if_b0_pending);
+#   - whatever zeroes the histogram zeroes the scratch and clears the flag
+#     (Metric._discard_lazy, GraphedUpdate._reset_states_inplace);
+#   - whatever replaces the scratch or the histogram flushes first.
+def take_b0_pending(owner) -> Optional[tuple]:
+    """(curve scratch, float32 thresholds) for the native flush if ``owner``'s
+    histogram is in pending format, else None. Clears the flag: the caller
+    flushes now, in the same native call that consumes the histogram."""
+    own = owner.__dict__
+    if not own.get("_hip_b0_pending"):
+        return None
+    own["_hip_b0_pending"] = False
+    plan = own.get("_hip_onepass_plan")  # None in a copy of the owner
+    src = owner.thresholds
+    thr = plan.thr if plan is not None and plan.thr_src is src else src.contiguous().float()
+    return own["_hip_onepass_scratch"], thr
+
+
+def flush_if_b0_pending(owner) -> None:
+    """Called by every writer of ``owner``'s histogram other than the one-pass
+    step: a pending histogram is flushed before they add to it."""
+    if owner.__dict__.get("_hip_b0_pending"):
+        owner._maybe_flush_lazy()
+
+
+def curve_resolve_pending(hist: Tensor, thresholds: Tensor, pending: Optional[Tensor]) -> None:
+    """The resolve kernel alone: complete the (C, T+1, 2) int64 ``hist`` in
+    place from ``pending`` = [P: C][R: C] (int64, zeroed by the kernel), for
+    float32 ``thresholds``. ``pending`` None: nothing is launched."""
+    C, T = hist.shape[0], hist.shape[1] - 1
+    assert hist.is_contiguous() and hist.dtype == torch.long and thresholds.dtype == torch.float32
+    assert thresholds.is_contiguous() and thresholds.numel() == T
+    assert pending is None or (pending.is_contiguous() and pending.dtype == torch.long and pending.numel() >= 2 * C)
+    rc = _lib().ma_curve_resolve_pending(
+        _stream(), hist.data_ptr(), C, T, thresholds.data_ptr(), pending.data_ptr() if pending is not None else 0
+    )
+    _check(rc, "ma_curve_resolve_pending")
+
+
+def onepass_scratch_layout(num_classes: int) -> dict:
+    """Offsets in u64 words of the one-pass curve scratch, as the Python side
+    reads it: ``P`` and ``R`` (``num_classes`` words each) lead, the per-block
+    records (2 words for each of 1024 blocks) and flag bytes (1024) follow.
+    ``words`` must equal ``ma_mc_onepass_scratch_words(num_classes)``."""
+    C = int(num_classes)
+    rec = 2 * C
+    flags = rec + 2 * 1024
+    return {"P": 0, "R": C, "records": rec, "flags": flags, "words": flags + 1024 // 8}
 
 
 def mc_stat_into(
@@ -1514,11 +1585,17 @@ def mc_onepass_update(
     # replace the state tensors: the next step rebuilds the plan. Until then
     # one stale set of states stays alive.
     own = curve.__dict__
+    if not own.get("_hip_b0_pending") and own.get("_lazy_dirty"):
+        # another writer filled the histogram since the last flush: its rows are
+        # not in P and R, so they are flushed before this step arms the format
+        curve._maybe_flush_lazy()
     tensors = (*step, own.get("_hip_hist_buf"), own.get("_hip_onepass_scratch"), thr_src)
     scalars = (dt, C, T, ignore_index, k)
     if plan is None or plan.scalars != scalars or not plan.fits(tensors):
-        # [P | N1 | N0 copies | per-block records | per-block flags]; the tail
-        # kernel re-zeroes the counters, records and flags are overwritten every step
+        # histogram or scratch may be replaced below: nothing may be owed then
+        flush_if_b0_pending(curve)
+        # [P | R | per-block records | per-block flags]; P and R are zeroed by
+        # the flush, records and flags are overwritten every step
         cs = owner_buffer(curve, "_hip_onepass_scratch", (cs_words,), torch.long, dev)
         hist = _pooled_hist(C, T, dev, curve)
         assert curve.confmat.is_contiguous()
@@ -1528,8 +1605,9 @@ def mc_onepass_update(
     mc_step_mark_mutated(step)
     # same lazy protocol as curve_hist_into_confmat: the histogram accumulates,
     # the suffix/confmat materialization waits for the first state read
-    curve.__dict__["_hip_lazy_meta"] = (C, T, 1)
-    curve.__dict__["_lazy_dirty"] = True
+    own["_hip_lazy_meta"] = (C, T, 1)
+    own["_lazy_dirty"] = True
+    own["_hip_b0_pending"] = True  # the histogram now lacks bucket b0 of the rows binned from registers
     return True
 
 
@@ -1730,8 +1808,10 @@ class _ComputePlan(_NativePlan):
         self.owned = (params_dev, cm_scratch, auc)
         self.n_formulas = n
 
-    def step(self, flush: bool):
-        """One native call, at most three launches. Returns (out, auc): a fresh
+    def step(self, flush: bool, pending: Optional[tuple] = None):
+        """One native call, at most three launches, one more in front of them
+        for ``pending`` = (curve scratch, float32 thresholds) of a histogram in
+        pending-b0 format (:func:`take_b0_pending`; with ``flush`` only). Returns (out, auc): a fresh
         ``[linear 0..n-1 | mcc, kappa, jaccard | exact]`` float32 buffer and the
         (C,) views ``(auroc, auroc weights, ap, ap weights)`` of the plan's own
         per-class buffer (None without a curve group; overwritten by the next
@@ -1742,6 +1822,7 @@ class _ComputePlan(_NativePlan):
         rc = _lib().ma_compute_plan_step(
             self.handle, _stream(), COMPUTE_FLUSH if flush else 0, out.data_ptr(),
             auc.data_ptr() if auc is not None else 0,
+            pending[0].data_ptr() if pending else 0, pending[1].data_ptr() if pending else 0,
         )
         _check(rc, "ma_compute_plan_step")
         return out, self.auc_views
