@@ -4,12 +4,13 @@
 // tp/fp/fn/confmat, online-softmax row stats, out-of-range epoch flag) and
 // then k_multiclass_curve_hist, which has to wait for a kernel boundary
 // because "softmax iff ANY element of the batch lies outside [0,1]" is a
-// batch-global decision. Here a wave owns a row and keeps the whole row in
-// registers (16 B per lane per vector, NV vectors per lane), so the row is
-// read from HBM once:
+// batch-global decision. Here a wave owns a row (or 64 / LPR rows, see ROW
+// GROUPS in front of the kernel) and keeps the whole row in registers (16 B
+// per lane per vector, NV vectors per lane), so the row is read from HBM once:
 //
 //  phase A  what k_mc_stat_logits does: both call softmax_fold /
-//           softmax_merge_wave and count_row of row_fold.h (8-wide groups for
+//           softmax_merge_wave (softmax_merge_group here: the same tree
+//           for a row held by fewer lanes) and count_row of row_fold.h (8-wide groups for
 //           bf16, 4-wide for fp32), so rowmax/rowinv are bit-identical to the
 //           two-kernel path by construction. The argmax is taken by value
 //           first and index after (wave_max_f32, row_argmax_index,
@@ -98,116 +99,200 @@ typedef unsigned long long ull;
 #define ONEPASS_FLAG_OFF(C) (ONEPASS_REC_OFF(C) + 2 * ONEPASS_GRID_MAX)
 #define ONEPASS_CS_WORDS(C) (ONEPASS_FLAG_OFF(C) + ONEPASS_GRID_MAX / 8)
 #define ONEPASS_TAIL_GRID_DEFAULT 4096  // blocks of k_onepass_tail, see onepass_step
+// defaults of the row-group mapping and the grid cap, see onepass_lpr / onepass_grid_cap
+// (sweep in profiles/README.md, "Row groups": more rows per wave save vector
+// instructions but no time, the prefetch with twice the tasks per wave does)
+#define ONEPASS_LPR_DEFAULT(nv) 64
+#define ONEPASS_GRID_DEFAULT(prefetch) ((prefetch) ? 512 : 1024)
+// the second row buffer of the prefetch costs 4 registers per vector: only for
+// slices of up to 4 vectors per lane, 2 with the top-k slot (nothing may spill)
+#define ONEPASS_PF_MAX_NVL 4
+#define ONEPASS_PREFETCH_DEFAULT 1
 
 // TOPK: the optional top-k stat slot (second scratch tp2|fp2|fn2, see
 // count_row_topk). A template parameter, so the instantiation without the slot
 // is the kernel it was before the slot existed.
-template <typename T_, int NV, bool TOPK>
-__global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_onepass(
+//
+// ROW GROUPS (template parameter LPR, lanes per row, 16 / 32 / 64): a row of
+// NV <= 2 vectors per lane is too short for a wave — the merges, the two
+// reductions, the first-lane section and every binning round cost the same
+// for 64 lanes as for 16. So a wave owns G = 64 / LPR consecutive rows at
+// once, one per group of LPR lanes (a 16-lane DPP row, a half wave, or the
+// wave: LPR = 64 is the one-row-per-wave kernel). Lane l of group g holds the
+// vectors l + LPR*j, j < NV*G, of row row0 + g. rowmax / rowinv keep their
+// bits through the virtual-lane order of softmax_merge_group (row_fold.h);
+// max, min, OR and the integer sums do not depend on the order. What was
+// wave-uniform per row (target, row statistics, argmax, ignored / certain /
+// bin_now, the rank) is per group now, i.e. a vector register; the cross-lane
+// steps never leave a group, and a group whose row lies past B holds zeros,
+// counts nothing, stores nothing and bins nothing while its lanes still take
+// part in every step.
+// Launch bounds = the waves per SIMD the grid really produces: at most 1024
+// blocks of 4 waves on 256 CUs, i.e. 4, which leaves 128 registers. NV = 8
+// needs more than 128 (3 waves), and so does the top-k slot on top of an
+// 8-vector slice (2). No instantiation needs scratch; without the top-k slot
+// none spills a scalar either, four with it spill 4-6 scalars to lanes
+// (profiles/README.md, "Row groups").
+#define ONEPASS_WAVES(NV, TOPK, LPR) ((NV) > 4 ? 3 : ((TOPK) && (NV) * (WAVE / (LPR)) == 8) ? 2 : 4)
+//
+// PREFETCH (template parameter PF): loads, stores and atomics of a wave share
+// one in-order counter, so a wait for the next task's row is also a wait for
+// every histogram atomic issued before it, and those take microseconds when
+// the whole chip issues them. With PF the next task's row and target are
+// requested into a second register buffer BEFORE phase A of the current one,
+// and the wave waits for them once, behind phase A and in front of its own
+// atomics: by then the previous task's atomics have had a whole phase A to
+// drain, and the ones it issues next are waited for by nobody until the next
+// task's phase A is done.
+template <typename T_, int NV, bool TOPK, int LPR, bool PF>
+__global__ void __launch_bounds__(256, ONEPASS_WAVES(NV, TOPK, LPR)) k_mc_onepass(
     const uint4* __restrict__ preds, const ll* __restrict__ target, ll B, ll C, ll ignore_index,
-    int has_ignore, ull* __restrict__ tp, ull* __restrict__ fp, ull* __restrict__ fn,
+    int has_ignore, ull* __restrict__ counts /* [tp|fp|fn]: 3*C */,
     ull* __restrict__ confmat, float* __restrict__ rowmax, float* __restrict__ rowinv,
     const float* __restrict__ thresholds, int T, int uniform, float t0, float inv_step,
-    ull* __restrict__ hist /* (C, T+1, 2) */, ull* __restrict__ cP /* C, cumulative */,
-    uint4* __restrict__ records /* gridDim.x */, unsigned char* __restrict__ flags /* gridDim.x */,
-    int topk, ull* __restrict__ tp2, ull* __restrict__ fp2, ull* __restrict__ fn2 /* TOPK only */) {
+    ull* __restrict__ hist /* (C, T+1, 2) */,
+    ull* __restrict__ cs /* curve scratch [P|R|records|flags]: P cumulative, one record and flag per block */,
+    int topk, ull* __restrict__ counts2 /* [tp2|fp2|fn2]: 3*C, TOPK only */) {
     constexpr int EPV = 16 / sizeof(T_);  // elements per 16-byte vector
+    constexpr int G = WAVE / LPR;         // rows per wave = virtual lanes per lane
+    constexpr int NVL = NV * G;           // vectors per lane
+    static_assert(NVL <= 8, "the row slice of a lane is at most 8 vectors (32 registers, 64 todo bits)");
     extern __shared__ float sthr[];
     __shared__ unsigned int block_valid, blk_outside, blk_binned, blk_deferred, blk_correct;
 
     const int lane = threadIdx.x & (WAVE - 1);
+    const int l = lane & (LPR - 1);                // lane inside the group
+    const int g = LPR == WAVE ? 0 : lane / LPR;    // group = row of the wave's task
     // wave-uniform by construction; tell the compiler, so the row index and
     // everything derived from it live in scalar registers
     const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     const int waves_per_block = blockDim.x / WAVE;
-    const ll row_stride = (ll)gridDim.x * waves_per_block;
+    const ll row_stride = (ll)gridDim.x * waves_per_block * G;
     const int nvec = (int)(C / EPV);  // C <= 4096 here: 32-bit class indices
     unsigned int outside = 0;
     unsigned int my_valid = 0, my_binned = 0, my_deferred = 0, my_correct = 0;
 
-    // the whole row, packed, in registers: vector k of this lane is pv[lane + 64*k]
-    uint4 r[NV];
-    auto load_row = [&](ll row) {
+    // the group's whole row, packed, in registers: vector j of this lane is
+    // pv[l + LPR*j]; a group past B holds zeros
+    uint4 r[NVL];
+    uint4 rn[PF ? NVL : 1];  // PF: the next task's row
+    ll t_next = 0;           // PF: and its target
+    auto load_row = [&](uint4* dst, ll row) {
+        const bool live = LPR == WAVE || row < B;
         const uint4* pv = preds + row * (ll)nvec;
 #pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const int v = lane + k * WAVE;
-            r[k] = v < nvec ? pv[v] : make_uint4(0u, 0u, 0u, 0u);
+        for (int j = 0; j < NVL; j++) {
+            const int v = l + j * LPR;
+            dst[j] = (live && v < nvec) ? pv[v] : make_uint4(0u, 0u, 0u, 0u);
         }
     };
-    // the first row's loads are in flight while the block stages the thresholds
-    ll row = (ll)blockIdx.x * waves_per_block + wave_in_block;
-    if (row < B) load_row(row);
+    auto load_target = [&](ll row) { return (LPR == WAVE || row < B) ? target[row] : 0; };
+    // the first rows' loads are in flight while the block stages the thresholds
+    ll row0 = ((ll)blockIdx.x * waves_per_block + wave_in_block) * G;  // first row of the wave's task
+    if (row0 < B) {
+        load_row(r, row0 + g);
+        if constexpr (PF) t_next = load_target(row0 + g);
+    }
     for (int b = threadIdx.x; b < T; b += blockDim.x) sthr[b] = thresholds[b];
     if (threadIdx.x == 0) { block_valid = 0; blk_outside = 0; blk_binned = 0; blk_deferred = 0; blk_correct = 0; }
     __syncthreads();
     const int b0 = bucket_of(0.0f, sthr, T);
     const float hi0 = b0 < T ? sthr[b0] : INFINITY;  // bucket b0 is [thr[b0-1], thr[b0])
+    // PF: the first row is waited for here, so that inside the loop nothing of
+    // the current row is ever pending and the only wait is the explicit one
+    if constexpr (PF) __builtin_amdgcn_s_waitcnt(0x0F70);
 
-    while (row < B) {
-        const ll t = target[row];
+    while (row0 < B) {
+        const ll row = row0 + g;
+        const bool live = LPR == WAVE || row < B;
+        ll t;
+        if constexpr (PF) {
+            t = t_next;
+            if (row0 + row_stride < B) {
+                load_row(rn, row0 + row_stride + g);
+                t_next = load_target(row0 + row_stride + g);
+            }
+        } else {
+            t = live ? target[row] : 0;
+        }
 
         // ---- phase A: the folds of k_mc_stat_logits (row_fold.h) ----
         // The row stays in registers, so the argmax index need not ride
         // through the fold: the fold keeps the lane's largest value (not the
         // softmax m, which starts at -3.4e38 rather than -inf), the index is
-        // looked up once the row's maximum is known.
+        // looked up once the row's maximum is known. One (max, sumexp) pair
+        // per virtual lane q; vector j = q + G*k is vector L + 64*k of virtual
+        // lane L = l + LPR*q, folded for k = 0, 1, ... as that lane would.
         float best = -INFINITY;
-        float sm_m = -3.4e38f, sm_s = 0.0f;  // online softmax (max, sumexp)
+        float sm_m[G], sm_s[G];  // online softmax (max, sumexp)
+#pragma unroll
+        for (int q = 0; q < G; q++) { sm_m[q] = -3.4e38f; sm_s[q] = 0.0f; }
         unsigned int row_out = 0;
 #pragma unroll
         for (int k = 0; k < NV; k++) {
-            const int v = lane + k * WAVE;
-            if (v < nvec) {
-                float f[EPV];
-                unpack16<T_>(r[k], f);
-                best = fmaxf(best, softmax_fold(f, sm_m, sm_s, row_out));
+#pragma unroll
+            for (int q = 0; q < G; q++) {
+                const int v = l + (q + G * k) * LPR;
+                if (v < nvec) {
+                    float f[EPV];
+                    unpack16<T_>(r[q + G * k], f);
+                    best = fmaxf(best, softmax_fold(f, sm_m[q], sm_s[q], row_out));
+                }
             }
         }
         // an ignored row takes no part in the softmax decision (the reference
         // drops ignored samples before the range test); t is already loaded
-        const bool ignored = has_ignore && t == ignore_index;
-        if (ignored) row_out = 0u;
+        const bool ignored = live && has_ignore && t == ignore_index;
+        if (ignored || !live) row_out = 0u;
         outside |= row_out;
-        softmax_merge_wave(sm_m, sm_s);
-        const float rowbest = wave_max_f32(best);
+        softmax_merge_group<LPR>(sm_m, sm_s);
+        const float rowbest = group_max_f32<LPR>(best);
         const unsigned int best_idx =
-            wave_min_u32(row_argmax_index<T_, NV>(r, lane, nvec, rowbest));  // 0x7fffffff: all NaN
-        // lane 0 holds the row's (max, sumexp); every lane needs them for phase B.
-        // All 64 lanes are active here, so lane 0 is the first active lane:
-        // the values come over as scalars, with no LDS round trip.
-        const float rmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sm_m)));
-        const float rsum = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sm_s)));
+            group_min_u32<LPR>(row_argmax_index<T_, NVL, LPR>(r, l, nvec, rowbest));  // 0x7fffffff: all NaN
+        // the group's first lane holds the row's (max, sumexp); every lane of
+        // the group needs them for phase B. All 64 lanes are active here.
+        const float rmax = group_first<LPR>(sm_m[0]);
+        const float rsum = group_first<LPR>(sm_s[0]);
         const float rinv = 1.0f / rsum;
-        const bool certain = __ballot(row_out != 0u) != 0ULL;  // this row alone proves "softmax"
-        const bool bin_now = certain && !ignored;
+        // this row alone proves "softmax": the group's slice of the ballot
+        const ull any_out = __ballot(row_out != 0u);
+        bool certain;
+        if constexpr (LPR == WAVE) certain = any_out != 0ULL;
+        else certain = ((any_out >> (g * LPR)) & ((1ULL << LPR) - 1ULL)) != 0ULL;
+        const bool bin_now = certain && !ignored && live;
         // ---- top-k slot: rank of x[t] among the row, from the registers ----
         // Needed only for a valid row whose argmax is not the target (a == t
-        // means rank 0); both are wave-uniform, so the count is skipped
-        // otherwise and lane 0 sees rank 0, which gives the same counts.
+        // means rank 0); the count is skipped when no group of the wave needs
+        // it, and a group that does not need it sees rank 0, which gives the
+        // same counts.
         unsigned int rank = 0;
         if constexpr (TOPK) {
-            if (!ignored && t >= 0 && t < C && best_idx < (unsigned int)C && (ll)best_idx != t) {
-                const float xt = row_element<T_, NV>(r, (int)t);
+            const bool need = live && !ignored && t >= 0 && t < C && best_idx < (unsigned int)C && (ll)best_idx != t;
+            if (__ballot(need) != 0ULL) {
+                const int te = need ? (int)t : 0;
+                const float xt = row_element<T_, NVL, LPR>(r, te, lane);
                 unsigned int cnt = 0;
 #pragma unroll
-                for (int k = 0; k < NV; k++) {
-                    const int v = lane + k * WAVE;
+                for (int j = 0; j < NVL; j++) {
+                    const int v = l + j * LPR;
                     if (v < nvec) {
                         float f[EPV];
-                        unpack16<T_>(r[k], f);
-                        rank_fold(f, v * EPV, xt, (int)t, cnt);
+                        unpack16<T_>(r[j], f);
+                        rank_fold(f, v * EPV, xt, te, cnt);
                     }
                 }
-                rank = wave_sum_u32(cnt);  // lane 0 holds the row's rank
+                cnt = group_sum_u32<LPR>(need ? cnt : 0u);  // the group's first lane holds the row's rank
+                rank = need ? cnt : 0u;
             }
         }
-        if (lane == 0) {
+        // PF: the one wait of the task (vmcnt(0) alone), see PREFETCH above
+        if constexpr (PF) __builtin_amdgcn_s_waitcnt(0x0F70);
+        if (l == 0 && live) {
             const ll p = (ll)best_idx;
-            if (count_row(t, p, C, ignored, tp, fp, fn, confmat)) {
+            if (count_row(t, p, C, ignored, counts, counts + C, counts + 2 * C, confmat)) {
                 my_valid++;
                 if (p == t) my_correct++;
-                if constexpr (TOPK) count_row_topk(t, p, rank, topk, tp2, fp2, fn2);
+                if constexpr (TOPK) count_row_topk(t, p, rank, topk, counts2, counts2 + C, counts2 + 2 * C);
             }
             rowmax[row] = rmax;
             // the done mark must compare < 0 whatever rinv is: a row with a NaN
@@ -216,25 +301,21 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             rowinv[row] = (bin_now || ignored) ? (rinv > 0.0f ? -rinv : -1.0f) : rinv;
             if (bin_now) {
                 my_binned++;
-                if (t >= 0 && t < C) atomicAdd(&cP[t], 1ULL);
+                if (t >= 0 && t < C) atomicAdd(&cs[t], 1ULL);  // P[t]
             } else if (!ignored) {
                 my_deferred++;
             }
         }
 
         // ---- phase B: bin from registers; bucket b0 stays pending until the flush ----
+        // bit j*EPV+i: element i of vector j needs the full path; 32 bits hold
+        // it for a slice of up to 32 elements. A lane whose row is not binned
+        // now keeps an empty queue.
+        typedef typename std::conditional<(EPV * NVL <= 32), unsigned int, ull>::type todo_t;
+        todo_t todo = 0;
+        // out-of-range targets bin with every label 0, like the two-kernel path
+        const int tc = (t >= 0 && t < C) ? (int)t : -1;
         if (bin_now) {
-            // out-of-range targets bin with every label 0, like the two-kernel path
-            const int tc = (t >= 0 && t < C) ? (int)t : -1;
-            auto bin_one = [&](float x, int c) {
-                const float p = expf(x - rmax) * rinv;
-                const int j = uniform ? bucket_of_uniform(p, sthr, T, t0, inv_step)
-                                      : bucket_of(p, sthr, T);
-                if (j != b0) {
-                    const int label = (tc == c) ? 1 : 0;
-                    atomicAdd(&hist[(ull)c * (T + 1) * 2 + j * 2 + label], 1ULL);
-                }
-            };
             // EXACT pre-filter in the logit domain. p = expf(d) * rinv with
             // d = x - rmax; bucket(p) == b0 <=> thr[b0-1] <= p < thr[b0].
             // The left half always holds (thr[b0-1] <= 0 <= p). For the right
@@ -255,47 +336,47 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
             // full path.
             const float dcut = logf(hi0 * rsum) - 1e-3f;
             const float xcut = (rmax + dcut) - fabsf(rmax) * 2.4e-7f;
-            // bit k*EPV+i: element i of vector k needs the full path; 32 bits
-            // hold it for all but bf16 NV=8
-            typedef typename std::conditional<(EPV * NV <= 32), unsigned int, ull>::type todo_t;
-            todo_t todo = 0;
 #pragma unroll
-            for (int k = 0; k < NV; k++) {
-                if (lane + k * WAVE < nvec) {
+            for (int j = 0; j < NVL; j++) {
+                if (l + j * LPR < nvec) {
                     float f[EPV];
-                    unpack16<T_>(r[k], f);
+                    unpack16<T_>(r[j], f);
 #pragma unroll
                     for (int i = 0; i < EPV; i++)
-                        todo |= (f[i] < xcut) ? (todo_t)0 : ((todo_t)1 << (k * EPV + i));
-                }
-            }
-            // compacted: every lane pops one pending element per round, so a
-            // row costs max-over-lanes(popcount) rounds, not EPV*NV
-            while (__ballot(todo != 0) != 0ULL) {
-                if (todo != 0) {
-                    int e;
-                    if constexpr (sizeof(todo_t) == 4) e = __ffs((int)todo) - 1;
-                    else e = __ffsll((ull)todo) - 1;
-                    todo &= todo - 1;
-                    const int wi = is_bf16_v<T_> ? (e >> 1) : e;  // 32-bit word of the row slice
-                    unsigned int w = r[0].x;
-#pragma unroll
-                    for (int q = 1; q < 4 * NV; q++) {
-                        const unsigned int cand = (q & 3) == 0 ? r[q >> 2].x
-                                                : (q & 3) == 1 ? r[q >> 2].y
-                                                : (q & 3) == 2 ? r[q >> 2].z
-                                                               : r[q >> 2].w;
-                        w = (wi == q) ? cand : w;
-                    }
-                    const float x = is_bf16_v<T_> ? __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16))
-                                            : __uint_as_float(w);
-                    const int k = e / EPV, i = e % EPV;
-                    bin_one(x, (lane + k * WAVE) * EPV + i);
+                        todo |= (f[i] < xcut) ? (todo_t)0 : ((todo_t)1 << (j * EPV + i));
                 }
             }
         }
-        row += row_stride;
-        if (row < B) load_row(row);  // r is dead here: same registers
+        // compacted: every lane pops one pending element per round, so a wave
+        // task costs max-over-lanes(popcount) rounds for all its rows together
+        while (__ballot(todo != 0) != 0ULL) {
+            if (todo != 0) {
+                int e;
+                if constexpr (sizeof(todo_t) == 4) e = __ffs((int)todo) - 1;
+                else e = __ffsll((ull)todo) - 1;
+                todo &= todo - 1;
+                const int wi = is_bf16_v<T_> ? (e >> 1) : e;  // 32-bit word of the row slice
+                const unsigned int w = row_slice_word<NVL>(r, wi);
+                const float x = is_bf16_v<T_> ? __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16))
+                                        : __uint_as_float(w);
+                const int j = e / EPV, i = e % EPV;
+                const int c = (l + j * LPR) * EPV + i;
+                const float p = expf(x - rmax) * rinv;
+                const int b = uniform ? bucket_of_uniform(p, sthr, T, t0, inv_step)
+                                      : bucket_of(p, sthr, T);
+                if (b != b0) {
+                    const int label = (tc == c) ? 1 : 0;
+                    atomicAdd(&hist[(ull)c * (T + 1) * 2 + b * 2 + label], 1ULL);
+                }
+            }
+        }
+        row0 += row_stride;
+        if constexpr (PF) {
+#pragma unroll
+            for (int j = 0; j < NVL; j++) r[j] = rn[j];
+        } else {
+            if (row0 < B) load_row(r, row0 + g);  // r is dead here: same registers
+        }
     }
     // the block's counts meet in LDS; nothing here touches a shared global word
     if (my_valid) atomicAdd(&block_valid, my_valid);
@@ -306,6 +387,8 @@ __global__ void __launch_bounds__(256, (NV <= 2 ? 8 : NV <= 4 ? 5 : 3)) k_mc_one
     __syncthreads();
     if (threadIdx.x == 0) {
         // one 16-byte store; a block holds < 2^31 rows, so bit 31 is free
+        uint4* records = (uint4*)(cs + ONEPASS_REC_OFF(C));
+        unsigned char* flags = (unsigned char*)(cs + ONEPASS_FLAG_OFF(C));
         records[blockIdx.x] = make_uint4(block_valid, blk_binned,
                                          blk_deferred | (blk_outside << 31), blk_correct);
         flags[blockIdx.x] = (unsigned char)((blk_deferred ? 1u : 0u) | (blk_outside ? 2u : 0u));
@@ -453,10 +536,10 @@ __global__ void __launch_bounds__(256) k_onepass_tail(
 
 extern "C" {
 
-// NV (16-byte vectors per lane) the one-pass kernel would use, 0 = unsupported
-// shape (caller keeps the two-kernel path). NV in {1,2,4,8}; NV <= 2 (bf16
-// C <= 1024, fp32 C <= 512) compiles to <= 64 VGPRs = 8 waves per SIMD, NV=4
-// to 5-7 and NV=8 to 3-4 waves, none with scratch (profiles/README.md).
+// NV (16-byte vectors per lane of a 64-lane row) the one-pass kernel would
+// use, 0 = unsupported shape (caller keeps the two-kernel path). NV in
+// {1,2,4,8}: bf16 C <= 1024 and fp32 C <= 512 are NV <= 2. Registers per
+// instantiation: profiles/README.md, none with scratch.
 int ma_mc_onepass_nv(int dtype /*0=f32 1=bf16*/, ll C, int T) {
     if (C <= 128 || T < 1 || (size_t)T * sizeof(float) > 48 * 1024) return 0;
     const int epv = dtype == 1 ? 8 : 4;
@@ -472,21 +555,50 @@ int ma_mc_onepass_nv(int dtype /*0=f32 1=bf16*/, ll C, int T) {
 // u64 words of the curve scratch for C classes (records region included)
 int ma_mc_onepass_scratch_words(ll C) { return (int)ONEPASS_CS_WORDS(C); }
 
-// blocks of k_mc_onepass for B rows: one row per wave and pass, 4 waves per
-// block. Measured at B=8192 C=1000 (sweep knob MA_ONEPASS_GRID): 2048 blocks —
-// every row resident at once — run the load, fold and binning phases chip-wide
-// in lock step (53 us/step); with 512-1024 blocks each wave takes several
-// rows, the waves drift apart and the phases overlap (45 us). The knob is
-// clamped to the records the scratch holds.
-static int onepass_grid(ll B) {
-    static int gcap = 0;
-    if (gcap == 0) {
-        const char* e = getenv("MA_ONEPASS_GRID");
-        gcap = e ? atoi(e) : 1024;
-        if (gcap < 64) gcap = 64;
-        if (gcap > ONEPASS_GRID_MAX) gcap = ONEPASS_GRID_MAX;
+static int onepass_lpr(int nv);
+// lanes per row a plan created now would run with (MA_ONEPASS_LPR included),
+// 0 = unsupported shape
+int ma_mc_onepass_lpr(int dtype, ll C, int T) {
+    const int nv = ma_mc_onepass_nv(dtype, C, T);
+    return nv ? onepass_lpr(nv) : 0;
+}
+
+// Lanes per row (LPR) for a kernel of NV vectors per 64-lane row: a lane holds
+// NV * 64 / LPR vectors, at most 8, so NV <= 2 may use 16, 32 or 64, NV = 4
+// 32 or 64, NV = 8 only 64. Default (sweep in profiles/README.md, "Row
+// groups"): one row per wave. Sweep knob MA_ONEPASS_LPR, read whenever a plan
+// is created; a value the shape does not support is raised to the next one it
+// does.
+static int onepass_lpr(int nv) {
+    const int min_lpr = nv <= 2 ? 16 : nv <= 4 ? 32 : 64;
+    int lpr = ONEPASS_LPR_DEFAULT(nv);
+    const char* e = getenv("MA_ONEPASS_LPR");
+    if (e) {
+        const int v = atoi(e);
+        if (v == 16 || v == 32 || v == 64) lpr = v;
     }
-    ll g = (B + 3) / 4;
+    return lpr < min_lpr ? min_lpr : lpr;
+}
+
+// Cap of the k_mc_onepass grid, sweep knob MA_ONEPASS_GRID, read whenever a
+// plan is created and clamped to the records the scratch holds. A wave task is
+// 64 / LPR consecutive rows, a block 4 waves. Measured at B=8192 C=1000 with
+// one row per task: 2048 blocks — every row resident at once — run the load,
+// fold and binning phases chip-wide in lock step (53 us/step); with 512-1024
+// blocks each wave takes several tasks, the waves drift apart and the phases
+// overlap (45 us). The prefetch variant wants more tasks per wave still: 512
+// blocks (profiles/README.md, "Row groups").
+static int onepass_grid_cap(int prefetch) {
+    const char* e = getenv("MA_ONEPASS_GRID");
+    int gcap = e ? atoi(e) : ONEPASS_GRID_DEFAULT(prefetch);
+    if (gcap < 64) gcap = 64;
+    if (gcap > ONEPASS_GRID_MAX) gcap = ONEPASS_GRID_MAX;
+    return gcap;
+}
+// blocks of k_mc_onepass for B rows
+static int onepass_grid(ll B, int lpr, int gcap) {
+    const ll tasks = (B + WAVE / lpr - 1) / (WAVE / lpr);
+    ll g = (tasks + 3) / 4;
     if (g > gcap) g = gcap;
     return (int)g;
 }
@@ -512,30 +624,40 @@ static int onepass_tail_cap() {
 struct OnepassPlan {
     McStep st;
     int dtype, nv, T, uniform;
+    int lpr, gcap, prefetch;  // lanes per row, grid cap, prefetch: fixed when the plan is created
     float t0, inv_step;
     ull *hist, *cscratch;
     const float* thresholds;
 };
 
-template <typename T_, int NV, bool TOPK>
+template <typename T_, int NV, bool TOPK, int LPR, bool PF>
 static void onepass_launch_main(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
-                                const ll* target, ll B, uint4* records, unsigned char* flags) {
+                                const ll* target, ll B) {
     const McStep& st = p.st;
     ull* sc = st.counts;
     ull* sc2 = TOPK ? st.topk_counts : nullptr;
-    k_mc_onepass<T_, NV, TOPK><<<grid, 256, (size_t)p.T * sizeof(float), s>>>(
-        (const uint4*)preds, target, B, st.C, st.ignore_index, (int)st.has_ignore, sc, sc + st.C,
-        sc + 2 * st.C, st.confmat, st.rowmax, st.rowinv, p.thresholds, p.T, p.uniform, p.t0,
-        p.inv_step, p.hist, p.cscratch, records, flags, (int)st.k, sc2,
-        TOPK ? sc2 + st.C : nullptr, TOPK ? sc2 + 2 * st.C : nullptr);
+    k_mc_onepass<T_, NV, TOPK, LPR, PF><<<grid, 256, (size_t)p.T * sizeof(float), s>>>(
+        (const uint4*)preds, target, B, st.C, st.ignore_index, (int)st.has_ignore, sc, st.confmat,
+        st.rowmax, st.rowinv, p.thresholds, p.T, p.uniform, p.t0, p.inv_step, p.hist, p.cscratch,
+        (int)st.k, sc2);
 }
 template <typename T_, bool TOPK>
 static void onepass_launch_nv(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
-                              const ll* target, ll B, uint4* records, unsigned char* flags) {
-    if (p.nv == 1) onepass_launch_main<T_, 1, TOPK>(p, s, grid, preds, target, B, records, flags);
-    else if (p.nv == 2) onepass_launch_main<T_, 2, TOPK>(p, s, grid, preds, target, B, records, flags);
-    else if (p.nv == 4) onepass_launch_main<T_, 4, TOPK>(p, s, grid, preds, target, B, records, flags);
-    else onepass_launch_main<T_, 8, TOPK>(p, s, grid, preds, target, B, records, flags);
+                              const ll* target, ll B) {
+    // (NV, LPR) pairs as onepass_lpr() hands them out
+#define ONEPASS_CASE(NV_, LPR_)                                                                    \
+    if (p.nv == NV_ && p.lpr == LPR_) {                                                            \
+        if constexpr (NV_ * (WAVE / LPR_) <= (TOPK ? ONEPASS_PF_MAX_NVL / 2 : ONEPASS_PF_MAX_NVL)) { \
+            if (p.prefetch)                                                                        \
+                return onepass_launch_main<T_, NV_, TOPK, LPR_, true>(p, s, grid, preds, target, B); \
+        }                                                                                          \
+        return onepass_launch_main<T_, NV_, TOPK, LPR_, false>(p, s, grid, preds, target, B);      \
+    }
+    ONEPASS_CASE(1, 16); ONEPASS_CASE(1, 32); ONEPASS_CASE(1, 64);
+    ONEPASS_CASE(2, 16); ONEPASS_CASE(2, 32); ONEPASS_CASE(2, 64);
+    ONEPASS_CASE(4, 32); ONEPASS_CASE(4, 64);
+    ONEPASS_CASE(8, 64);
+#undef ONEPASS_CASE
 }
 template <typename T_, bool TOPK>
 static void onepass_launch_tail(const OnepassPlan& p, hipStream_t s, int tgrid, int grid,
@@ -552,9 +674,9 @@ static void onepass_launch_tail(const OnepassPlan& p, hipStream_t s, int tgrid, 
 // the dtype and slot dispatch of both kernels, written once
 template <bool TOPK>
 static void onepass_launch_main_dt(const OnepassPlan& p, hipStream_t s, int grid, const void* preds,
-                                   const ll* target, ll B, uint4* records, unsigned char* flags) {
-    if (p.dtype == 0) onepass_launch_nv<float, TOPK>(p, s, grid, preds, target, B, records, flags);
-    else onepass_launch_nv<unsigned short, TOPK>(p, s, grid, preds, target, B, records, flags);
+                                   const ll* target, ll B) {
+    if (p.dtype == 0) onepass_launch_nv<float, TOPK>(p, s, grid, preds, target, B);
+    else onepass_launch_nv<unsigned short, TOPK>(p, s, grid, preds, target, B);
 }
 template <bool TOPK>
 static void onepass_launch_tail_dt(const OnepassPlan& p, hipStream_t s, int tgrid, int grid,
@@ -573,10 +695,10 @@ static int onepass_step(const OnepassPlan& p, hipStream_t s, uintptr_t preds, ui
     const ll C = p.st.C;
     uint4* records = (uint4*)(p.cscratch + ONEPASS_REC_OFF(C));
     unsigned char* flags = (unsigned char*)(p.cscratch + ONEPASS_FLAG_OFF(C));
-    const int grid = B > 0 ? onepass_grid(B) : 0;
+    const int grid = B > 0 ? onepass_grid(B, p.lpr, p.gcap) : 0;
     if (B > 0) {
-        if (p.st.k > 0) onepass_launch_main_dt<true>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
-        else onepass_launch_main_dt<false>(p, s, grid, (const void*)preds, (const ll*)target, B, records, flags);
+        if (p.st.k > 0) onepass_launch_main_dt<true>(p, s, grid, (const void*)preds, (const ll*)target, B);
+        else onepass_launch_main_dt<false>(p, s, grid, (const void*)preds, (const ll*)target, B);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -628,9 +750,16 @@ int ma_onepass_plan_create(const McStep* st, int dtype, uintptr_t thresholds, in
         return -103;
     if (st->k > 0 && (!st->topk_counts || !st->tp_k || !st->fp_k || !st->tn_k || !st->fn_k))
         return -103;
+    const int lpr = onepass_lpr(nv);
+    // sweep knob MA_ONEPASS_PREFETCH, see PREFETCH in front of k_mc_onepass; the
+    // variant exists where the second row buffer fits (onepass_launch_nv)
+    const char* pf = getenv("MA_ONEPASS_PREFETCH");
+    const int prefetch = (pf ? atoi(pf) != 0 : ONEPASS_PREFETCH_DEFAULT) &&
+                         nv * (WAVE / lpr) <= (st->k > 0 ? ONEPASS_PF_MAX_NVL / 2 : ONEPASS_PF_MAX_NVL);
     *handle = (unsigned long long)(uintptr_t) new OnepassPlan{
-        *st, dtype, nv, T, uniform, t0, inv_step, (ull*)hist, (ull*)cscratch,
-        (const float*)thresholds};
+        *st, dtype, nv, T, uniform, lpr, onepass_grid_cap(prefetch), prefetch,
+        t0, inv_step, (ull*)hist,
+        (ull*)cscratch, (const float*)thresholds};
     return 0;
 }
 

@@ -146,6 +146,83 @@ __device__ __forceinline__ unsigned int wave_min_u32(unsigned int x) {
     return (unsigned int)__shfl((int)x, 0);
 #endif
 }
+
+// ---- row groups: LPR lanes per row, 64 / LPR rows per wave ----
+// A group is LPR consecutive lanes, LPR in {16, 32, 64}: a 16-lane DPP row, a
+// half wave, or the wave. Every function below needs all 64 lanes active and
+// never moves a value from one group into another, so the groups of a wave may
+// hold unrelated rows (or none). LPR = 64 is the wave function above, with its
+// wave-uniform result.
+//
+// max / min over the group, returned to every lane of it: the quad swaps and
+// row rotates of the wave butterfly; a 32-lane group adds the swap of its two
+// 16-lane rows.
+template <int LPR>
+__device__ __forceinline__ float group_max_f32(float x) {
+    static_assert(LPR == 16 || LPR == 32 || LPR == 64, "lanes per row");
+    if constexpr (LPR == 64) {
+        return wave_max_f32(x);
+    } else {
+#if MA_ROWFOLD_XLANE
+        auto step = [](float v, int o) { return fmaxf(v, __int_as_float(o)); };
+        x = step(x, MA_DPP_STEP(__float_as_int(x), 0xb1, 0xf));
+        x = step(x, MA_DPP_STEP(__float_as_int(x), 0x4e, 0xf));
+        x = step(x, MA_DPP_STEP(__float_as_int(x), 0x124, 0xf));
+        x = step(x, MA_DPP_STEP(__float_as_int(x), 0x128, 0xf));
+        if constexpr (LPR == 32) {
+            const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+            x = fmaxf(__uint_as_float(p[0]), __uint_as_float(p[1]));
+        }
+#else
+        for (int off = LPR / 2; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
+#endif
+        return x;
+    }
+}
+template <int LPR>
+__device__ __forceinline__ unsigned int group_min_u32(unsigned int x) {
+    static_assert(LPR == 16 || LPR == 32 || LPR == 64, "lanes per row");
+    if constexpr (LPR == 64) {
+        return wave_min_u32(x);
+    } else {
+#if MA_ROWFOLD_XLANE
+        auto step = [](unsigned int v, int o) { return min(v, (unsigned int)o); };
+        x = step(x, MA_DPP_STEP((int)x, 0xb1, 0xf));
+        x = step(x, MA_DPP_STEP((int)x, 0x4e, 0xf));
+        x = step(x, MA_DPP_STEP((int)x, 0x124, 0xf));
+        x = step(x, MA_DPP_STEP((int)x, 0x128, 0xf));
+        if constexpr (LPR == 32) {
+            const auto p = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+            x = min(p[0], p[1]);
+        }
+#else
+        for (int off = LPR / 2; off > 0; off >>= 1) x = min(x, (unsigned int)__shfl_xor((int)x, off));
+#endif
+        return x;
+    }
+}
+// value of the group's first lane, returned to every lane of the group: a row
+// broadcast of lane 0 of each 16-lane row; in a 32-lane group the odd rows then
+// take the even row's (the first result of the half-row swap).
+template <int LPR>
+__device__ __forceinline__ unsigned int group_first_u32(unsigned int x) {
+    static_assert(LPR == 16 || LPR == 32 || LPR == 64, "lanes per row");
+    if constexpr (LPR == 64) {
+        return (unsigned int)__builtin_amdgcn_readfirstlane((int)x);
+    } else {
+#if MA_ROWFOLD_XLANE
+        x = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)x, 0x150, 0xf, 0xf, false);  // row_newbcast:0
+        if constexpr (LPR == 32) x = __builtin_amdgcn_permlane16_swap(x, x, false, false)[0];
+        return x;
+#else
+        return (unsigned int)__shfl((int)x, 0, LPR);
+#endif
+    }
+}
+template <int LPR>
+__device__ __forceinline__ float group_first(float x) {
+    return __uint_as_float(group_first_u32<LPR>(__float_as_uint(x)));
+}
 #undef MA_DPP_STEP
 
 // ---- online softmax: (m, s) = (running max, sum of exp(x - m)) ----
@@ -194,6 +271,32 @@ __device__ __forceinline__ void softmax_merge_wave(float& m, float& s) {
     softmax_merge_step(m, s, lane_down<1>(m), lane_down<1>(s));
 }
 
+// The same merge for a row held by a group of LPR lanes (see "row groups").
+// VIRTUAL LANES: lane l of the group stands for the lanes L = l + LPR*q,
+// q < Q = 64 / LPR, of a wave that holds the row alone, and keeps one (m, s)
+// pair per q, folded over exactly the vectors L + 64*k that lane L folds, in
+// the same order. The tree of softmax_merge_wave pairs L with L + off: while
+// off >= LPR that is the pair (q, q + off / LPR) of one lane, below it the
+// same lane_down step, which never leaves a 16-lane row (lane_down<16> pairs
+// the two rows of a 32-lane group). Same operands, same order, same rounding:
+// m[0], s[0] of the group's first lane are bit for bit what lane 0 of the wave
+// form holds. The other pairs are scratch afterwards.
+template <int LPR>
+__device__ __forceinline__ void softmax_merge_group(float (&m)[64 / LPR], float (&s)[64 / LPR]) {
+    static_assert(LPR == 16 || LPR == 32 || LPR == 64, "lanes per row");
+#pragma unroll
+    for (int off = 32; off >= LPR; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < off / LPR; q++) softmax_merge_step(m[q], s[q], m[q + off / LPR], s[q + off / LPR]);
+    }
+    if constexpr (LPR == 64) softmax_merge_step(m[0], s[0], lane_down<32>(m[0]), lane_down<32>(s[0]));
+    if constexpr (LPR >= 32) softmax_merge_step(m[0], s[0], lane_down<16>(m[0]), lane_down<16>(s[0]));
+    softmax_merge_step(m[0], s[0], lane_down<8>(m[0]), lane_down<8>(s[0]));
+    softmax_merge_step(m[0], s[0], lane_down<4>(m[0]), lane_down<4>(s[0]));
+    softmax_merge_step(m[0], s[0], lane_down<2>(m[0]), lane_down<2>(s[0]));
+    softmax_merge_step(m[0], s[0], lane_down<1>(m[0]), lane_down<1>(s[0]));
+}
+
 // ---- argmax, lowest index on a tie (torch.argmax); c = index of f[0] ----
 template <int K, typename Idx>
 __device__ __forceinline__ void argmax_fold(const float (&f)[K], Idx c, float& best,
@@ -222,15 +325,16 @@ __device__ __forceinline__ void argmax_merge_wave(float& best, Idx& best_idx) {
 // row_argmax_index(): the lowest index this lane holds with f == rowbest
 // (+0.0 and -0.0 tie, as they do under > and ==; a row of -inf matches at its
 // first -inf; NaN matches nothing), and wave_min_u32 over the lanes.
-// r[k] is vector lane + 64*k of the row; vectors at or past nvec hold no data.
-template <typename T, int NV>
+// r[j] is vector lane + LPR*j of the row, lane counted inside the row's group
+// (LPR = 64: the wave); vectors at or past nvec hold no data.
+template <typename T, int NV, int LPR = 64>
 __device__ __forceinline__ unsigned int row_argmax_index(const uint4 (&r)[NV], int lane, int nvec,
                                                          float rowbest) {
     constexpr int EPV = 16 / sizeof(T);
     unsigned int idx = 0x7fffffffu;
 #pragma unroll
     for (int k = NV - 1; k >= 0; k--) {  // descending: the lowest match is written last
-        const int v = lane + k * 64;
+        const int v = lane + k * LPR;
         if (v < nvec) {
             float f[EPV];
             unpack16<T>(r[k], f);
@@ -272,25 +376,40 @@ __device__ __forceinline__ void rank_fold(const float (&f)[K], Idx c, float xt, 
     for (int i = 0; i < K; i++) cnt += (f[i] > xt || (f[i] == xt && c + i < t)) ? 1u : 0u;
 }
 
-// element e of a row held in registers (r[k] is vector lane + 64*k of the
-// row), returned to every lane: the 32-bit word is picked out of the lane's
-// registers and read from the lane that holds it. e must be wave-uniform and
-// inside the row. No memory access.
-template <typename T, int NV>
-__device__ __forceinline__ float row_element(const uint4 (&r)[NV], int e) {
+// 32-bit word wi (per lane, 0 <= wi < 4*NV) of the lane's row slice r[0..NV):
+// registers cannot be indexed per lane, so the word comes out of a binary
+// select tree over the bits of wi — one compare per bit and 4*NV - 1 selects,
+// where a chain of (wi == q) tests pays a compare per word. NV a power of two.
+template <int NV>
+__device__ __forceinline__ unsigned int row_slice_word(const uint4 (&r)[NV], int wi) {
+    static_assert((NV & (NV - 1)) == 0, "power of two");
+    unsigned int w[4 * NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) { w[4 * k] = r[k].x; w[4 * k + 1] = r[k].y; w[4 * k + 2] = r[k].z; w[4 * k + 3] = r[k].w; }
+#pragma unroll
+    for (int bit = 0; (1 << bit) < 4 * NV; bit++) {
+        const bool odd = ((wi >> bit) & 1) != 0;
+#pragma unroll
+        for (int i = 0; i < ((4 * NV) >> (bit + 1)); i++) w[i] = odd ? w[2 * i + 1] : w[2 * i];
+    }
+    return w[0];
+}
+
+// element e of a row held in registers by a group of LPR lanes (r[j] is vector
+// lane + LPR*j of the row), returned to every lane of the group: the 32-bit
+// word is picked out of the lane's registers and read from the lane that holds
+// it. e must be the same in every lane of a group and inside the row; with
+// LPR = 64 it is wave-uniform and the word comes over as a scalar, a narrower
+// group reads it with a lane-indexed shuffle. All 64 lanes must be active. No
+// memory access.
+template <typename T, int NV, int LPR = 64>
+__device__ __forceinline__ float row_element(const uint4 (&r)[NV], int e, int lane = 0) {
     constexpr int EPV = 16 / sizeof(T);
     const int vec = e / EPV, i = e % EPV;
-    const int wi = (vec >> 6) * 4 + (is_bf16_v<T> ? (i >> 1) : i);  // word of the lane's slice
-    unsigned int w = r[0].x;
-#pragma unroll
-    for (int q = 1; q < 4 * NV; q++) {
-        const unsigned int cand = (q & 3) == 0 ? r[q >> 2].x
-                                : (q & 3) == 1 ? r[q >> 2].y
-                                : (q & 3) == 2 ? r[q >> 2].z
-                                               : r[q >> 2].w;
-        w = (wi == q) ? cand : w;
-    }
-    w = (unsigned int)__builtin_amdgcn_readlane((int)w, vec & 63);
+    const int wi = (vec / LPR) * 4 + (is_bf16_v<T> ? (i >> 1) : i);  // word of the lane's slice
+    unsigned int w = row_slice_word<NV>(r, wi);
+    if constexpr (LPR == 64) w = (unsigned int)__builtin_amdgcn_readlane((int)w, vec & 63);
+    else w = (unsigned int)__shfl((int)w, (lane & ~(LPR - 1)) | (vec & (LPR - 1)));
     if constexpr (is_bf16_v<T>) return __uint_as_float((i & 1) ? (w & 0xffff0000u) : (w << 16));
     else return __uint_as_float(w);
 }
@@ -300,6 +419,19 @@ __device__ __forceinline__ float row_element(const uint4 (&r)[NV], int e) {
 __device__ __forceinline__ unsigned int wave_sum_u32(unsigned int x) {
     x += lane_down_u32<32>(x);
     x += lane_down_u32<16>(x);
+    x += lane_down_u32<8>(x);
+    x += lane_down_u32<4>(x);
+    x += lane_down_u32<2>(x);
+    x += lane_down_u32<1>(x);
+    return x;
+}
+// the same over a group of LPR lanes: the steps that stay inside the group;
+// the sum lands in the group's first lane
+template <int LPR>
+__device__ __forceinline__ unsigned int group_sum_u32(unsigned int x) {
+    static_assert(LPR == 16 || LPR == 32 || LPR == 64, "lanes per row");
+    if constexpr (LPR == 64) x += lane_down_u32<32>(x);
+    if constexpr (LPR >= 32) x += lane_down_u32<16>(x);
     x += lane_down_u32<8>(x);
     x += lane_down_u32<4>(x);
     x += lane_down_u32<2>(x);

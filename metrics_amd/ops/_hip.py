@@ -183,6 +183,7 @@ _SIGNATURES = {
     "ma_compute_plan_step": [_U64, _U64, _I, _U64, _U64, _U64, _U64],
     "ma_linear_stat_multi": [_U64, _U64, _U64, _U64, _U64, _LL, _I, _U64, _U64],
     "ma_mc_onepass_nv": [_I, _LL, _I],
+    "ma_mc_onepass_lpr": [_I, _LL, _I],
     "ma_mc_onepass_scratch_words": [_LL],
     "ma_onepass_plan_create": [_STEP_P, _I, _U64, _I, _I, _F, _F, _U64, _U64, ctypes.POINTER(ctypes.c_ulonglong)],
     "ma_onepass_plan_step": [_U64, _U64, _U64, _U64, _LL],
