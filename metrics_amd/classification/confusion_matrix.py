@@ -36,6 +36,7 @@ from metrics_amd.functional.classification.confusion_matrix import (
 class BinaryConfusionMatrix(Metric):
     """(2,2) confusion matrix for binary tasks (stateful)."""
 
+    _hip_fused_kind = "bin_confmat"
     is_differentiable = False
     higher_is_better = None
     full_state_update: bool = False

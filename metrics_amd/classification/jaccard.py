@@ -29,6 +29,7 @@ from metrics_amd.functional.classification.confusion_matrix import (
 class BinaryJaccardIndex(Metric):
     """Jaccard index for binary tasks (stateful)."""
 
+    _hip_fused_kind = "bin_confmat"  # the (2, 2) state and update of BinaryConfusionMatrix
     is_differentiable = False
     higher_is_better = True
     full_state_update: bool = False

@@ -45,6 +45,7 @@ def _curve_kernels_cover(thresholds: Tensor) -> bool:
 class BinaryPrecisionRecallCurve(Metric):
     """PR curve for binary tasks (stateful)."""
 
+    _hip_fused_kind = "bin_curve"
     is_differentiable: bool = False
     higher_is_better: Optional[bool] = None
     full_state_update: bool = False

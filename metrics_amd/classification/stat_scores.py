@@ -84,6 +84,7 @@ class _AbstractStatScores(Metric):
 class BinaryStatScores(_AbstractStatScores):
     """tp/fp/tn/fn counts for binary tasks."""
 
+    _hip_fused_kind = "bin_stat"
     is_differentiable: bool = False
     higher_is_better: Optional[bool] = None
     full_state_update: bool = False

@@ -335,6 +335,96 @@ class _FusedMultilabelUpdatePlan:
         return handled
 
 
+class _FusedBinaryUpdatePlan:
+    """Collection-level fusion for binary metrics: the leaders of the
+    stat-scores, confusion-matrix and threshold-curve groups all need the same
+    per-element facts (label, ignored, ``x > cut``, bucket of the probability),
+    so ONE native call of two launches (``csrc/bin_step.hip``) reads the
+    predictions and the int64 targets once, as a flat stream, and feeds all of
+    them. At least two participants; a stat leader is not required.
+
+    The groups keep their own normalisation decisions (stat: any element
+    outside [0, 1]; confusion matrix and curve: any element that is not
+    ignored). Inside a plan the confusion-matrix leader thresholds with the
+    exact rule of the stat kernel (``x > logit(threshold)`` when the batch is
+    normalised) instead of comparing a rounded ``sigmoid(x)``: see
+    docs/PARITY.md. ``METRICS_AMD_FUSE_BINARY=0`` builds no plan."""
+
+    def __init__(self, stat, confmat, curve):
+        self.stat = stat
+        self.confmat = confmat
+        self.curve = curve
+        self.leaders = tuple(m for m in (stat, confmat, curve) if m is not None)
+        self.ignore_index = self.leaders[0].ignore_index
+        # two participants and one curve leader at most: one of these exists
+        self.threshold = next(m.threshold for m in (stat, confmat) if m is not None)
+        self.steps = 0
+        self.curve_steps = 0
+
+    @staticmethod
+    def build(collection) -> "Optional[_FusedBinaryUpdatePlan]":
+        from metrics_amd.ops import _hip
+
+        if not _hip.fuse_binary_enabled():
+            return None
+        found = {"bin_stat": None, "bin_confmat": None, "bin_curve": None}
+        for members in collection._groups.values():
+            leader = getattr(collection, members[0])
+            kind = getattr(type(leader), "_hip_fused_kind", None)
+            if kind not in found or found[kind] is not None:
+                continue  # the first leader of each kind; further groups stay on their own
+            if getattr(leader, "validate_args", True) or not _updates_as_marked(leader):
+                continue  # validations are skipped on the fused path
+            if getattr(leader, "multidim_average", "global") != "global":
+                continue
+            if kind == "bin_curve" and leader.thresholds is None:
+                continue
+            found[kind] = leader
+        stat, confmat, curve = found["bin_stat"], found["bin_confmat"], found["bin_curve"]
+        participants = [m for m in (stat, confmat, curve) if m is not None]
+        if len(participants) < 2:
+            return None
+        if len({m.ignore_index for m in participants}) != 1:
+            return None
+        if len({float(m.threshold) for m in (stat, confmat) if m is not None}) > 1:
+            return None
+        return _FusedBinaryUpdatePlan(stat, confmat, curve)
+
+    def try_run(self, *args: Any, **kwargs: Any) -> tuple:
+        """Run the fused step if the inputs qualify; returns the handled leaders
+        (empty tuple -> every leader updates on its own)."""
+        if kwargs or len(args) != 2:
+            return ()
+        preds, target = args
+        if not (isinstance(preds, Tensor) and isinstance(target, Tensor) and preds.is_cuda and target.is_cuda):
+            return ()
+        if preds.dtype not in (torch.float32, torch.bfloat16) or not preds.is_contiguous():
+            return ()
+        if target.dtype != torch.long or target.shape != preds.shape or not target.is_contiguous():
+            return ()
+        if target.device != preds.device:
+            return ()
+        from metrics_amd.ops import _hip
+
+        if not _hip.hip_available():
+            return ()
+        stat, confmat, curve = self.stat, self.confmat, self.curve
+        # above the LDS gate the curve leader updates on its own, the rest still fuses
+        if curve is not None and curve.thresholds.numel() > _hip.BIN_STEP_MAX_T:
+            curve = None
+        handled = self.leaders if curve is self.curve else tuple(m for m in self.leaders if m is not self.curve)
+        if len(handled) < 2:
+            return ()
+        if not _hip.bin_step_update(
+            preds, target, self.ignore_index, self.threshold, stat=stat, confmat=confmat, curve=curve,
+        ):
+            return ()
+        self.steps += 1
+        if curve is not None:
+            self.curve_steps += 1
+        return handled
+
+
 class _FusedMulticlassComputePlan:
     """Collection-level compute: every member that declares what it computes
     (``Metric._compute_plan_spec``) over the stat-scores, confusion-matrix,
@@ -526,6 +616,7 @@ class MetricCollection(ModuleDict):
         super().__init__()
         self._fused_plan: Any = False
         self._fused_ml_plan: Any = False
+        self._fused_bin_plan: Any = False
         self._compute_plan: Any = False
         self.prefix = self._check_arg(prefix, "prefix")
         self.postfix = self._check_arg(postfix, "postfix")
@@ -568,6 +659,14 @@ class MetricCollection(ModuleDict):
             if self._fused_ml_plan is not None and not fused_done:
                 with tracing.range("MetricCollection.fused_ml_update"):
                     fused_done = self._fused_ml_plan.try_run(*args, **kwargs)
+            # the binary plan, likewise of kinds of its own; built by the first
+            # step neither other plan handled
+            if not fused_done:
+                if self._fused_bin_plan is False:
+                    self._fused_bin_plan = _FusedBinaryUpdatePlan.build(self)
+                if self._fused_bin_plan is not None:
+                    with tracing.range("MetricCollection.fused_bin_update"):
+                        fused_done = self._fused_bin_plan.try_run(*args, **kwargs)
             # run only each group's leader
             # identity check: Metric.__eq__ is the compositional operator
             # (returns a CompositionalMetric, which is always truthy)

@@ -159,7 +159,60 @@ def ml_step(num_labels: int, ignore_index: Optional[int], threshold: float, t: M
     return rec
 
 
+class BinStepTensors(NamedTuple):
+    """The tensor objects one fused binary step works on, by name. Every
+    optional group is None when absent."""
+
+    counts: Tensor  # (6,) int64 count scratch: the step fills it, the tail zeroes it
+    records: Tensor  # one uint8 per block of the step kernel
+    tp: Optional[Tensor] = None  # the four stat states, one element each
+    fp: Optional[Tensor] = None
+    tn: Optional[Tensor] = None
+    fn: Optional[Tensor] = None
+    confmat: Optional[Tensor] = None  # (2, 2) state
+    thresholds: Optional[Tensor] = None  # the curve group: float32 thresholds,
+    hist: Optional[Tensor] = None  # the lazy (1, T+1, 2) histogram,
+    curve_scratch: Optional[Tensor] = None  # the per-step (2, T+1, 2) scratch, zero between steps,
+    epoch_buf: Optional[Tensor] = None  # and the device epoch E
+
+
+class BinStep(ctypes.Structure):
+    """Mirror of ``BinStep`` in csrc/bin_step.h, field for field. ``_load`` holds
+    field names, order and size against the header."""
+
+    _fields_ = [
+        ("ignore_index", _LL), ("has_ignore", _LL), ("thr", _D),
+        ("counts", _U64), ("records", _U64),
+        ("tp", _U64), ("fp", _U64), ("tn", _U64), ("fn", _U64), ("confmat", _U64),
+        ("T", _LL), ("thresholds", _U64), ("uniform", _LL), ("t0", _D), ("inv_step", _D),
+        ("hist", _U64), ("curve_scratch", _U64), ("epoch_buf", _U64),
+    ]
+
+
+_BIN_STEP_P = ctypes.POINTER(BinStep)
+
+
+def bin_step(ignore_index: Optional[int], threshold: float, t: BinStepTensors,
+             uniform: tuple = (0, 0.0, 1.0)) -> BinStep:
+    """The record of one binary step over the tensors ``t``, filled by name. The
+    curve group is on iff ``t.thresholds`` is given; ``uniform`` = its
+    :func:`_uniform_params`. It holds bare addresses: whoever keeps the record
+    keeps ``t`` next to it."""
+    rec = BinStep(ignore_index=ignore_index if ignore_index is not None else 0,
+                  has_ignore=ignore_index is not None, thr=float(threshold))
+    for name, x in zip(t._fields, t):
+        if x is not None:
+            setattr(rec, name, x.data_ptr())
+    if t.thresholds is not None:
+        rec.T = t.thresholds.shape[0]
+        rec.uniform, rec.t0, rec.inv_step = uniform
+    return rec
+
+
 _SIGNATURES = {
+    "ma_bin_step": [_U64, _BIN_STEP_P, _U64, _I, _U64, _LL],
+    "ma_bin_step_layout": [_LL, _I, _I, ctypes.POINTER(_LL)],
+    "ma_bin_step_sizeof": [],
     "ma_ml_step": [_U64, _ML_STEP_P, _U64, _I, _U64, _LL],
     "ma_ml_step_layout": [_LL, _LL, _I, ctypes.POINTER(_LL)],
     "ma_ml_step_sizeof": [],
@@ -228,6 +281,19 @@ def _declare_argtypes(lib: ctypes.CDLL) -> None:
             f"MlStep: the Python mirror {mirror} and csrc/ml_step.h {ml_step_native_fields(lib)} differ in"
             " field names, order or size; rebuild the library"
         )
+    lib.ma_bin_step_field_names.argtypes = []
+    lib.ma_bin_step_field_names.restype = ctypes.c_char_p
+    mirror = [name for name, _ in BinStep._fields_]
+    if bin_step_native_fields(lib) != mirror or lib.ma_bin_step_sizeof() != ctypes.sizeof(BinStep):
+        raise RuntimeError(
+            f"BinStep: the Python mirror {mirror} and csrc/bin_step.h {bin_step_native_fields(lib)} differ in"
+            " field names, order or size; rebuild the library"
+        )
+
+
+def bin_step_native_fields(lib: ctypes.CDLL) -> list:
+    """The field names of the native ``BinStep`` in declaration order."""
+    return lib.ma_bin_step_field_names().decode().rstrip(",").split(",")
 
 
 def mc_step_native_fields(lib: ctypes.CDLL) -> list:
@@ -1746,6 +1812,127 @@ def ml_step_update(
         # same lazy protocol as curve_hist_into_confmat: the histogram
         # accumulates, the suffix/confmat materialization waits for a state read
         curve.__dict__["_hip_lazy_meta"] = (L, T, 1)
+        curve.__dict__["_lazy_dirty"] = True
+    return True
+
+
+# Fused binary step (csrc/bin_step.hip). METRICS_AMD_FUSE_BINARY=0 keeps every
+# leader of a binary collection on its own update path, exactly as before (A/B
+# lever, escape hatch and the oracle of the tests). Read when a collection
+# builds its plan.
+FUSE_BINARY_ENV = "METRICS_AMD_FUSE_BINARY"
+
+# Largest threshold count with which the curve leader rides the fused step: the
+# step kernel keeps the histogram twice in LDS (raw and sigmoid),
+# [2][T+1][2] u32 plus the T float thresholds, next to 256 bytes of static LDS
+# (block counters), against the 160 KiB of a gfx950 workgroup:
+# 16*(T+1) + 4*T + 256 <= 163840, i.e. 20*T <= 163568 (BIN_LDS_BYTES /
+# BIN_LDS_STATIC in csrc/bin_step.hip). Above it the curve leader updates on
+# its own and the other leaders still fuse.
+BIN_STEP_MAX_T = (160 * 1024 - 256 - 16) // 20  # 8178
+
+_BIN_LAYOUT_CACHE: dict = {}
+
+
+def fuse_binary_enabled() -> bool:
+    return os.environ.get(FUSE_BINARY_ENV, "1") != "0"
+
+
+def bin_step_layout(numel: int, dtype_code: int, num_thresholds: int) -> Optional[tuple]:
+    """(record bytes, elements per unit, elements per vector, step blocks, tail
+    blocks, dynamic LDS bytes, histogram copies per block) of a fused binary
+    step over ``numel`` elements of fp32 (``dtype_code`` 0) or bf16 (1) at a
+    16-byte aligned address, None where the kernels do not cover the shape.
+    ``num_thresholds`` 0: no curve leader. Host only."""
+    key = (numel, dtype_code, num_thresholds)
+    if key not in _BIN_LAYOUT_CACHE:
+        out = (_LL * 7)()
+        rc = _lib().ma_bin_step_layout(numel, dtype_code, num_thresholds, out)
+        if len(_BIN_LAYOUT_CACHE) > 256:
+            _BIN_LAYOUT_CACHE.clear()
+        _BIN_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _BIN_LAYOUT_CACHE[key]
+
+
+def bin_step_update(
+    preds: Tensor, target: Tensor, ignore_index: Optional[int], threshold: float,
+    stat=None, confmat=None, curve=None,
+) -> bool:
+    """The whole step of a fused binary collection in ONE native call of two
+    launches that reads the fp32 / bf16 ``preds`` (any shape, read as a flat
+    stream) and the int64 ``target`` once: the stat counts into the ``stat``
+    leader's tp/fp/tn/fn, [[tn, fp], [fn, tp]] into the ``confmat`` leader's
+    state, and the threshold-curve histogram into the ``curve`` leader's lazy
+    buffer (absent leaders are None). Every buffer lives in the ``__dict__`` of
+    the leader it serves (:func:`owner_buffer`); no allocation, fill or host
+    sync in steady state. Both inputs must be contiguous.
+
+    Returns False without launching anything where the kernels do not cover
+    the shape: the caller lets every leader update on its own.
+    """
+    lib = _lib()
+    dt = _dtype_code(preds)
+    N = preds.numel()
+    dev = preds.device
+    base = stat if stat is not None else confmat if confmat is not None else curve
+    thr, T = None, 0
+    if curve is not None:
+        src = curve.thresholds
+        hit = curve.__dict__.get("_hip_bin_thr")
+        if hit is not None and hit[0] is src:
+            thr = hit[1]
+        else:
+            thr = src.contiguous().float()
+            curve.__dict__["_hip_bin_thr"] = (src, thr)
+        T = thr.numel()
+    lay = bin_step_layout(N, dt, T)
+    if lay is None:
+        return False
+    if curve is not None:
+        flush_if_b0_pending(curve)  # never pending for a binary leader; the rule of every histogram writer
+    tensors = BinStepTensors(
+        counts=owner_buffer(base, "_hip_bin_counts", (6,), torch.long, dev),
+        records=owner_buffer(base, "_hip_bin_records", (lay[0],), torch.uint8, dev),
+        tp=stat.tp if stat is not None else None,
+        fp=stat.fp if stat is not None else None,
+        tn=stat.tn if stat is not None else None,
+        fn=stat.fn if stat is not None else None,
+        confmat=confmat.confmat if confmat is not None else None,
+    )
+    if curve is not None:
+        tensors = tensors._replace(
+            thresholds=thr,
+            hist=_pooled_hist(1, T, dev, curve),
+            curve_scratch=owner_buffer(curve, "_hip_bin_curve_scratch", (2, T + 1, 2), torch.long, dev),
+            epoch_buf=_epoch_buf(dev, curve),
+        )
+    # the record holds the addresses of everything that stays the same from
+    # step to step; reset() and a move to another device replace state tensors
+    # and the next step rebuilds it (the identity rule of _NativePlan.fits)
+    scalars = (ignore_index, float(threshold), T)
+    kept = base.__dict__.get("_hip_bin_rec")
+    if kept is not None and kept.scalars == scalars and all(map(operator.is_, kept.tensors, tensors)):
+        rec = kept.rec
+    else:
+        for name in ("tp", "fp", "tn", "fn", "confmat"):
+            x = getattr(tensors, name)
+            if x is not None and not (x.is_contiguous() and x.dtype == torch.long and x.device == dev):
+                return False
+        rec = bin_step(ignore_index, threshold, tensors, _uniform_params(thr) if curve is not None else (0, 0.0, 1.0))
+        base.__dict__["_hip_bin_rec"] = _MlStepRecord(tensors, scalars, rec)
+    rc = lib.ma_bin_step(_stream(), rec, preds.data_ptr(), dt, target.data_ptr(), N)
+    if rc == -103:
+        return False  # nothing was launched
+    _check(rc, "ma_bin_step")
+    for name in ("tp", "fp", "tn", "fn", "confmat"):
+        x = getattr(tensors, name)
+        if x is not None:
+            _mark_kernel_mutated(x)
+    if curve is not None:
+        # same lazy protocol as curve_hist_into_confmat for a binary owner: the
+        # histogram accumulates, the suffix/confmat materialization waits for a
+        # state read
+        curve.__dict__["_hip_lazy_meta"] = (1, T, 0)
         curve.__dict__["_lazy_dirty"] = True
     return True
 

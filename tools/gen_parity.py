@@ -43,6 +43,16 @@ DEVIATIONS = """## Known value deviations
   the torch path only in the rounding band around the cut-off
   (`0 < x < ~1e-7` for fp32 at `thr = 0.5`, a wider band for bf16).
   `METRICS_AMD_FUSE_MULTILABEL=0` keeps every leader on its own path.
+- The same inside a fused binary collection plan (`_FusedBinaryUpdatePlan`,
+  docs/ARCHITECTURE.md "Fused binary step"): the confusion-matrix leader
+  (`BinaryConfusionMatrix`, `BinaryMatthewsCorrCoef`, `BinaryJaccardIndex`,
+  `BinaryCohenKappa`) thresholds `x > logit(thr)` when its batch is normalised,
+  where its stand-alone update compares `sigmoid(x)`, rounded to bf16 for bf16
+  inputs, with `thr`. The two differ only inside that rounding band. Which
+  batches are normalised does not change: the stat group decides over all
+  elements, confusion matrix and curve over the elements that are not ignored,
+  as on their own paths. `METRICS_AMD_FUSE_BINARY=0` keeps every leader on its
+  own path.
 """
 
 
