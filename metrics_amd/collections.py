@@ -425,6 +425,77 @@ class _FusedBinaryUpdatePlan:
         return handled
 
 
+class _FusedRankingUpdatePlan:
+    """Collection-level fusion for the multilabel ranking metrics: coverage
+    error, ranking average precision and ranking loss all come from the same
+    per-row counts, so ONE native call of two launches (``csrc/ml_rank.hip``)
+    with the combined ``want`` mask reads the scores and the int64 targets once
+    and adds into the states of every leader. At least two leaders.
+
+    The plan is additive: its leaders are of a kind no other plan takes, so it
+    runs whether or not another plan handled the step, and a multilabel
+    collection with stat, curve and ranking members takes one ``ml_step`` call
+    and one ranking call. ``METRICS_AMD_RANKING_KERNEL=0`` builds no plan."""
+
+    def __init__(self, leaders):
+        self.leaders = tuple(leaders)
+        self.num_labels = self.leaders[0].num_labels
+        self.ignore_index = self.leaders[0].ignore_index
+        self.steps = 0
+
+    @staticmethod
+    def build(collection) -> "Optional[_FusedRankingUpdatePlan]":
+        from metrics_amd.ops import _hip
+
+        if not _hip.ranking_kernel_enabled():
+            return None
+        found: Dict[str, Any] = {}
+        for members in collection._groups.values():
+            leader = getattr(collection, members[0])
+            if getattr(type(leader), "_hip_fused_kind", None) != "ml_rank":
+                continue
+            measure = getattr(type(leader), "_rank_measure", None)
+            if measure is None or measure in found:
+                continue  # the first leader of each measure; further groups stay on their own
+            if getattr(leader, "validate_args", True) or not _updates_as_marked(leader):
+                continue  # validations are skipped on the fused path
+            found[measure] = leader
+        leaders = list(found.values())
+        if len(leaders) < 2:
+            return None
+        if len({m.num_labels for m in leaders}) != 1 or len({m.ignore_index for m in leaders}) != 1:
+            return None
+        return _FusedRankingUpdatePlan(leaders)
+
+    def try_run(self, *args: Any, **kwargs: Any) -> tuple:
+        """Run the fused call if the inputs qualify; returns the handled leaders
+        (empty tuple -> every leader updates on its own)."""
+        if kwargs or len(args) != 2:
+            return ()
+        preds, target = args
+        if not (isinstance(preds, Tensor) and isinstance(target, Tensor) and preds.is_cuda and target.is_cuda):
+            return ()
+        if preds.ndim != 2 or preds.dtype not in (torch.float32, torch.bfloat16) or not preds.is_contiguous():
+            return ()
+        if target.dtype != torch.long or target.shape != preds.shape or not target.is_contiguous():
+            return ()
+        if preds.shape[1] != self.num_labels or target.device != preds.device:
+            return ()
+        from metrics_amd.functional.classification.ranking import _ranking_kernel_inputs
+        from metrics_amd.ops import _hip
+
+        if not _hip.hip_available():
+            return ()
+        inputs = _ranking_kernel_inputs(preds, target, self.num_labels)
+        if inputs is None:
+            return ()
+        pairs = {type(m)._rank_measure: (m.measure, m.total) for m in self.leaders}
+        if not _hip.ml_ranking_into(inputs[0], inputs[1], self.ignore_index, owner=self.leaders[0], **pairs):
+            return ()
+        self.steps += 1
+        return self.leaders
+
+
 class _FusedMulticlassComputePlan:
     """Collection-level compute: every member that declares what it computes
     (``Metric._compute_plan_spec``) over the stat-scores, confusion-matrix,
@@ -617,6 +688,7 @@ class MetricCollection(ModuleDict):
         self._fused_plan: Any = False
         self._fused_ml_plan: Any = False
         self._fused_bin_plan: Any = False
+        self._fused_rank_plan: Any = False
         self._compute_plan: Any = False
         self.prefix = self._check_arg(prefix, "prefix")
         self.postfix = self._check_arg(postfix, "postfix")
@@ -667,6 +739,13 @@ class MetricCollection(ModuleDict):
                 if self._fused_bin_plan is not None:
                     with tracing.range("MetricCollection.fused_bin_update"):
                         fused_done = self._fused_bin_plan.try_run(*args, **kwargs)
+            # the ranking plan is additive: its leaders are of a kind none of
+            # the plans above takes, so it runs next to whichever of them ran
+            if self._fused_rank_plan is False:
+                self._fused_rank_plan = _FusedRankingUpdatePlan.build(self)
+            if self._fused_rank_plan is not None:
+                with tracing.range("MetricCollection.fused_rank_update"):
+                    fused_done = (*fused_done, *self._fused_rank_plan.try_run(*args, **kwargs))
             # run only each group's leader
             # identity check: Metric.__eq__ is the compositional operator
             # (returns a CompositionalMetric, which is always truthy)

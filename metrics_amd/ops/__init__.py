@@ -115,6 +115,15 @@ def multilabel_stat_scores_fused(
     return _hip.multilabel_stat(preds, target, threshold, ignore_index)
 
 
+def multilabel_ranking_sums(
+    scores: Tensor, target: Tensor, ignore_index: Optional[int], want: int = 7
+) -> Optional[Tensor]:
+    """GPU ranking sums over the normalised (N, L) scores: a (3, 2) fp32 tensor,
+    rows coverage / LRAP / loss (``want`` bits 1 / 2 / 4), columns (measure,
+    total). None where the kernel does not cover the shape."""
+    return _hip.ml_ranking_sums(scores, target, ignore_index, want)
+
+
 def binary_curve_confmat(
     preds: Tensor, target: Tensor, thresholds: Tensor, ignore_index: Optional[int] = None
 ) -> Tensor:

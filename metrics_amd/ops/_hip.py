@@ -216,6 +216,8 @@ _SIGNATURES = {
     "ma_ml_step": [_U64, _ML_STEP_P, _U64, _I, _U64, _LL],
     "ma_ml_step_layout": [_LL, _LL, _I, ctypes.POINTER(_LL)],
     "ma_ml_step_sizeof": [],
+    "ma_ml_rank": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
+    "ma_ml_rank_layout": [_LL, _LL, ctypes.POINTER(_LL)],
     "ma_mc_stat_logits": [_U64, _STEP_P, _U64, _I, _U64, _LL, _U64],
     "ma_mc_stat_topk_covers": [_LL],
     "ma_mc_stat_labels": [_U64, _STEP_P, _U64, _U64, _LL],
@@ -1935,6 +1937,113 @@ def bin_step_update(
         curve.__dict__["_hip_lazy_meta"] = (1, T, 0)
         curve.__dict__["_lazy_dirty"] = True
     return True
+
+
+# Multilabel ranking measures (csrc/ml_rank.hip). METRICS_AMD_RANKING_KERNEL=0
+# keeps the torch path of functional/classification/ranking.py everywhere,
+# exactly as before (A/B lever, escape hatch and an oracle of the tests). Read
+# at every call, and when a collection builds its plan.
+RANKING_KERNEL_ENV = "METRICS_AMD_RANKING_KERNEL"
+
+# Largest label count the kernel covers: a block stages one row in LDS as fp32
+# scores plus the u16 indices of the relevant labels, 6 bytes per label (the row
+# padded to a multiple of 4), behind 256 bytes of block scratch, against the
+# 160 KiB of a gfx950 workgroup: 6*L + 256 <= 163840 (RANK_LDS_BYTES /
+# RANK_LDS_STATIC / RANK_LABEL_BYTES in csrc/ml_rank.hip). Above it the torch
+# path runs.
+ML_RANK_MAX_L = (160 * 1024 - 256) // 6 // 4 * 4  # 27264
+
+RANK_WANT_COVERAGE, RANK_WANT_LRAP, RANK_WANT_LOSS = 1, 2, 4
+
+_RANK_LAYOUT_CACHE: dict = {}
+_RANK_FUNCTIONAL_OWNERS: dict = {}
+
+
+class _RankOwner:
+    """Holds the scratch of the functional form, one per device."""
+
+
+def ranking_kernel_enabled() -> bool:
+    return os.environ.get(RANKING_KERNEL_ENV, "1") != "0"
+
+
+def ml_rank_layout(rows: int, num_labels: int) -> Optional[tuple]:
+    """(waves per row, rows per block and pass, blocks, dynamic LDS bytes, slab
+    entries, last L of the wave-per-row mapping, largest L covered) of a
+    ranking call, None where the kernel does not cover the shape. Host only."""
+    key = (rows, num_labels)
+    if key not in _RANK_LAYOUT_CACHE:
+        out = (_LL * 7)()
+        rc = _lib().ma_ml_rank_layout(rows, num_labels, out)
+        if len(_RANK_LAYOUT_CACHE) > 256:
+            _RANK_LAYOUT_CACHE.clear()
+        _RANK_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _RANK_LAYOUT_CACHE[key]
+
+
+def _rank_state_ok(pair, dev) -> bool:
+    return all(
+        isinstance(x, Tensor) and x.dtype == torch.float32 and x.numel() == 1 and x.device == dev and x.is_contiguous()
+        for x in pair
+    )
+
+
+def ml_ranking_into(
+    preds: Tensor, target: Tensor, ignore_index: Optional[int],
+    coverage: Optional[Tuple[Tensor, Tensor]] = None,
+    lrap: Optional[Tuple[Tensor, Tensor]] = None,
+    loss: Optional[Tuple[Tensor, Tensor]] = None,
+    owner=None,
+) -> bool:
+    """The ranking sums of one batch in ONE native call of two launches, added
+    in place into the ``(measure, total)`` pairs given (one-element fp32
+    tensors; an absent measure is None). ``preds`` holds the already normalised
+    (N, L) fp32 / bf16 scores, ``target`` the int64 targets, both contiguous;
+    ``ignore_index`` is applied in the kernel. The fp64 slab lives in the
+    ``__dict__`` of ``owner`` (:func:`owner_buffer`); no allocation, fill or
+    host sync in steady state.
+
+    Returns False without launching anything where the kernel does not cover
+    the shape or a state: the caller runs the torch path.
+    """
+    lib = _lib()
+    dt = _dtype_code(preds)
+    N, L = preds.shape
+    dev = preds.device
+    pairs = (coverage, lrap, loss)
+    want = sum(bit for bit, pair in zip((RANK_WANT_COVERAGE, RANK_WANT_LRAP, RANK_WANT_LOSS), pairs) if pair is not None)
+    if want == 0 or N == 0:
+        return False
+    lay = ml_rank_layout(N, L)
+    if lay is None or not all(_rank_state_ok(pair, dev) for pair in pairs if pair is not None):
+        return False
+    if owner is None:
+        owner = _RANK_FUNCTIONAL_OWNERS.get(dev)
+        if owner is None:
+            owner = _RANK_FUNCTIONAL_OWNERS[dev] = _RankOwner()
+    slab = owner_buffer(owner, "_hip_rank_slab", (lay[4] * 4,), torch.float64, dev, zero=False)
+    ptrs = [x.data_ptr() if pair is not None else 0 for pair in pairs for x in (pair or (None, None))]
+    rc = lib.ma_ml_rank(
+        _stream(), preds.data_ptr(), dt, target.data_ptr(), N, L,
+        ignore_index if ignore_index is not None else 0, int(ignore_index is not None), want,
+        slab.data_ptr(), *ptrs,
+    )
+    if rc == -103:
+        return False  # nothing was launched
+    _check(rc, "ma_ml_rank")
+    return True
+
+
+def ml_ranking_sums(preds: Tensor, target: Tensor, ignore_index: Optional[int], want: int) -> Optional[Tensor]:
+    """Functional form: the sums of one batch as a fresh (3, 2) fp32 tensor,
+    rows coverage / LRAP / loss, columns (measure, total); rows ``want`` does
+    not name stay zero. None where the kernel does not cover the shape."""
+    out = torch.zeros(3, 2, dtype=torch.float32, device=preds.device)
+    pairs = [(out[i, 0], out[i, 1]) if want & bit else None
+             for i, bit in enumerate((RANK_WANT_COVERAGE, RANK_WANT_LRAP, RANK_WANT_LOSS))]
+    if not ml_ranking_into(preds, target, ignore_index, *pairs):
+        return None
+    return out
 
 
 # Collection compute plan (csrc/mc_compute.hip). METRICS_AMD_COMPUTE_PLAN=0

@@ -53,6 +53,30 @@ DEVIATIONS = """## Known value deviations
   elements, confusion matrix and curve over the elements that are not ignored,
   as on their own paths. `METRICS_AMD_FUSE_BINARY=0` keeps every leader on its
   own path.
+- Multilabel ranking metrics on the GPU (`csrc/ml_rank.hip`,
+  docs/ARCHITECTURE.md "Multilabel ranking kernel"). Coverage error and
+  ranking average precision are functions of the tie classes alone and equal
+  the torch path; the kernel forms every batch sum in fp64 and rounds the fp32
+  state once per update, where the torch path sums rows in fp32.
+  - Ranking loss, tie rule. The reference ranks with an unstable
+    `argsort().argsort()`, which leaves the value open when a relevant and an
+    irrelevant label of a row have the same score (bf16 sigmoids tie heavily,
+    fp32 sigmoids saturate to 1.0 from about x = 17). The kernel uses the
+    position under a STABLE ascending sort,
+    `inv_j = #{k : s_k < s_j} + #{k < j : s_k == s_j}`, one of the outcomes the
+    reference can produce. Ties
+    among relevant labels only, or among irrelevant ones only, do not change
+    the loss.
+  - Coverage error with `ignore_index`. The reference writes `-4L` into the
+    score of an ignored element and does not exclude it from the row minimum,
+    so a row with at least one ignored element "covers" all L labels, whatever
+    its relevant labels score. The kernel reproduces this on purpose
+    (coverage = L for such a row); it is a quirk of the reference, not a
+    choice of this project.
+  - NaN scores. The kernel never faults and every comparison with a NaN is
+    false, but the values of a row that holds one are unspecified and need not
+    equal the torch path (whose `unique` and `argsort` order NaN last).
+  - `METRICS_AMD_RANKING_KERNEL=0` keeps the torch path everywhere.
 """
 
 
