@@ -244,6 +244,99 @@ def _updates_as_marked(leader) -> bool:
     return False
 
 
+class _FusedSpatialUpdatePlan:
+    """Collection-level fusion for multiclass metrics fed (N, C, *spatial)
+    predictions with an (N, *spatial) target (dense prediction): ONE native
+    call of two launches (``csrc/mc_spatial.hip``) reads the predictions where
+    they lie, without the transposed (N*S, C) copy every stand-alone update
+    makes, and feeds the leaders of the stat-scores, confusion-matrix,
+    exact-match and threshold-curve groups. It takes the leader kinds and the
+    qualification rules of :class:`_FusedMulticlassUpdatePlan`, which declines
+    such inputs; at least two participants, a stat leader is not required.
+    ``METRICS_AMD_FUSE_SPATIAL=0`` builds no plan."""
+
+    def __init__(self, stat, confmat, exact, curve):
+        self.stat = stat
+        self.confmat = confmat
+        self.exact = exact
+        self.curve = curve
+        self.leaders = tuple(m for m in (stat, confmat, exact, curve) if m is not None)
+        self.num_classes = self.leaders[0].num_classes
+        self.ignore_index = self.leaders[0].ignore_index
+        self.steps = 0
+        self.curve_steps = 0
+
+    @staticmethod
+    def build(collection) -> "Optional[_FusedSpatialUpdatePlan]":
+        from metrics_amd.ops import _hip
+
+        if not _hip.fuse_spatial_enabled():
+            return None
+        found = {"mc_stat": None, "mc_confmat": None, "mc_exact": None, "mc_curve": None}
+        for members in collection._groups.values():
+            leader = getattr(collection, members[0])
+            kind = getattr(type(leader), "_hip_fused_kind", None)
+            if kind not in found or found[kind] is not None:
+                continue  # the first leader of each kind; further groups stay on their own
+            if getattr(leader, "validate_args", True) or not _updates_as_marked(leader):
+                continue  # validations are skipped on the fused path
+            if getattr(leader, "multidim_average", "global") != "global":
+                continue
+            if kind == "mc_stat" and (getattr(leader, "top_k", 1) != 1 or leader.num_classes is None):
+                continue
+            if kind == "mc_curve" and (
+                leader.thresholds is None
+                or not _hip.curve_kernels_cover(leader.thresholds.numel())
+                or getattr(leader, "average", None) == "micro"
+            ):
+                continue
+            found[kind] = leader
+        stat, confmat, exact, curve = found["mc_stat"], found["mc_confmat"], found["mc_exact"], found["mc_curve"]
+        participants = [m for m in (stat, confmat, exact, curve) if m is not None]
+        if len(participants) < 2:
+            return None
+        if len({m.num_classes for m in participants}) != 1 or len({m.ignore_index for m in participants}) != 1:
+            return None
+        return _FusedSpatialUpdatePlan(stat, confmat, exact, curve)
+
+    def try_run(self, *args: Any, **kwargs: Any) -> tuple:
+        """Run the fused step if the inputs qualify; returns the handled leaders
+        (empty tuple -> every leader updates on its own)."""
+        if kwargs or len(args) != 2:
+            return ()
+        preds, target = args
+        if not (isinstance(preds, Tensor) and isinstance(target, Tensor) and preds.is_cuda and target.is_cuda):
+            return ()
+        if preds.ndim < 3 or preds.dtype not in (torch.float32, torch.bfloat16) or not preds.is_contiguous():
+            return ()
+        C = self.num_classes
+        if preds.shape[1] != C:
+            return ()
+        if target.dtype != torch.long or not target.is_contiguous() or target.device != preds.device:
+            return ()
+        if target.shape != (preds.shape[0], *preds.shape[2:]):
+            return ()
+        from metrics_amd.ops import _hip
+
+        if not _hip.hip_available() or C > _hip.MC_SPATIAL_MAX_C:
+            return ()
+        stat, confmat, exact, curve = self.stat, self.confmat, self.exact, self.curve
+        # above the LDS gate the curve leader updates on its own, the rest still fuses
+        if curve is not None and not _hip.mc_spatial_curve_rides(C, curve.thresholds.numel()):
+            curve = None
+        handled = self.leaders if curve is self.curve else tuple(m for m in self.leaders if m is not self.curve)
+        if len(handled) < 2:
+            return ()
+        if not _hip.mc_spatial_step_update(
+            preds, target, C, self.ignore_index, stat=stat, confmat=confmat, exact=exact, curve=curve,
+        ):
+            return ()
+        self.steps += 1
+        if curve is not None:
+            self.curve_steps += 1
+        return handled
+
+
 class _FusedMultilabelUpdatePlan:
     """Collection-level fusion for multilabel metrics: the leaders of the
     stat-scores, confusion-matrix, exact-match and threshold-curve groups all
@@ -689,6 +782,7 @@ class MetricCollection(ModuleDict):
         self._fused_ml_plan: Any = False
         self._fused_bin_plan: Any = False
         self._fused_rank_plan: Any = False
+        self._fused_sp_plan: Any = False
         self._compute_plan: Any = False
         self.prefix = self._check_arg(prefix, "prefix")
         self.postfix = self._check_arg(postfix, "postfix")
@@ -724,6 +818,15 @@ class MetricCollection(ModuleDict):
             if self._fused_plan is not None:
                 with tracing.range("MetricCollection.fused_update"):
                     fused_done = self._fused_plan.try_run(*args, **kwargs)
+            # the spatial plan takes the (N, C, *spatial) inputs the plan above
+            # declines, for the same leader kinds; built by the first step that
+            # plan did not handle
+            if not fused_done:
+                if self._fused_sp_plan is False:
+                    self._fused_sp_plan = _FusedSpatialUpdatePlan.build(self)
+                if self._fused_sp_plan is not None:
+                    with tracing.range("MetricCollection.fused_spatial_update"):
+                        fused_done = self._fused_sp_plan.try_run(*args, **kwargs)
             # the multilabel plan: its leaders are of other kinds, so a
             # collection runs at most one of the two
             if self._fused_ml_plan is False:

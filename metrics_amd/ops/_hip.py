@@ -10,6 +10,7 @@ updates must never silently fall back to stock torch kernels on MI355X.
 from __future__ import annotations
 
 import ctypes
+import math
 import operator
 import os
 from typing import NamedTuple, Optional, Tuple
@@ -209,7 +210,75 @@ def bin_step(ignore_index: Optional[int], threshold: float, t: BinStepTensors,
     return rec
 
 
+class McSpatialStepTensors(NamedTuple):
+    """The tensor objects one fused spatial multiclass step works on, by name.
+    Every optional group is None when absent."""
+
+    counts: Tensor  # [tp|fp|fn], (3*C,) int64 count scratch: the step fills it, the tail zeroes it
+    records: Tensor  # three int32 per block of the step kernel
+    tp: Optional[Tensor] = None  # the four stat states, (C,) each
+    fp: Optional[Tensor] = None
+    tn: Optional[Tensor] = None
+    fn: Optional[Tensor] = None
+    confmat: Optional[Tensor] = None  # (C, C) state, counted into directly
+    correct: Optional[Tensor] = None  # the exact-match states, with rowbad
+    total: Optional[Tensor] = None
+    rowbad: Optional[Tensor] = None  # (>=N,) int32 mismatch words, zero between steps
+    thresholds: Optional[Tensor] = None  # the curve group: float32 thresholds,
+    hist: Optional[Tensor] = None  # the lazy (C, T+1, 2) histogram,
+    epoch_buf: Optional[Tensor] = None  # the device epoch E,
+    rowstats: Optional[Tensor] = None  # (2, >=N*S) float32 [rowmax; rowinv] in row order (n, s)
+    tile_flags: Optional[Tensor] = None  # and one uint8 per wave tile, zero between steps
+
+
+class McSpatialStep(ctypes.Structure):
+    """Mirror of ``McSpatialStep`` in csrc/mc_spatial.h, field for field.
+    ``_load`` holds field names, order and size against the header."""
+
+    _fields_ = [
+        ("C", _LL), ("ignore_index", _LL), ("has_ignore", _LL),
+        ("counts", _U64), ("records", _U64),
+        ("tp", _U64), ("fp", _U64), ("tn", _U64), ("fn", _U64), ("confmat", _U64),
+        ("correct", _U64), ("total", _U64), ("rowbad", _U64), ("sample_cap", _LL),
+        ("T", _LL), ("thresholds", _U64), ("uniform", _LL), ("t0", _D), ("inv_step", _D),
+        ("hist", _U64), ("epoch_buf", _U64), ("rowmax", _U64), ("rowinv", _U64), ("row_cap", _LL),
+        ("tile_flags", _U64), ("tile_cap", _LL),
+    ]
+
+
+_MC_SPATIAL_STEP_P = ctypes.POINTER(McSpatialStep)
+
+
+def mc_spatial_step(num_classes: int, ignore_index: Optional[int], t: McSpatialStepTensors,
+                    uniform: tuple = (0, 0.0, 1.0)) -> McSpatialStep:
+    """The record of one spatial step over ``num_classes`` classes and the
+    tensors ``t``, filled by name. The curve group is on iff ``t.thresholds`` is
+    given; ``uniform`` = its :func:`_uniform_params`. It holds bare addresses:
+    whoever keeps the record keeps ``t`` next to it."""
+    rec = McSpatialStep(C=num_classes, ignore_index=ignore_index if ignore_index is not None else 0,
+                        has_ignore=ignore_index is not None)
+    for name, x in zip(t._fields, t):
+        if x is not None and name != "rowstats":
+            setattr(rec, name, x.data_ptr())
+    if t.rowbad is not None:
+        rec.sample_cap = t.rowbad.shape[0]
+    if t.thresholds is not None:
+        rec.T = t.thresholds.shape[0]
+        rec.uniform, rec.t0, rec.inv_step = uniform
+        rec.row_cap = t.rowstats.shape[1]
+        rec.rowmax = t.rowstats.data_ptr()
+        rec.rowinv = rec.rowmax + 4 * rec.row_cap
+        rec.tile_cap = t.tile_flags.shape[0]
+    return rec
+
+
 _SIGNATURES = {
+    "ma_mc_spatial_step": [_U64, _MC_SPATIAL_STEP_P, _U64, _I, _U64, _LL, _LL],
+    "ma_mc_spatial_layout": [_LL, _LL, _LL, _I, _I, ctypes.POINTER(_LL)],
+    "ma_mc_spatial_step_sizeof": [],
+    "ma_mc_spatial_max_classes": [],
+    "ma_mc_spatial_lds_bytes": [],
+    "ma_mc_spatial_lds_static": [],
     "ma_bin_step": [_U64, _BIN_STEP_P, _U64, _I, _U64, _LL],
     "ma_bin_step_layout": [_LL, _I, _I, ctypes.POINTER(_LL)],
     "ma_bin_step_sizeof": [],
@@ -291,6 +360,24 @@ def _declare_argtypes(lib: ctypes.CDLL) -> None:
             f"BinStep: the Python mirror {mirror} and csrc/bin_step.h {bin_step_native_fields(lib)} differ in"
             " field names, order or size; rebuild the library"
         )
+    lib.ma_mc_spatial_step_field_names.argtypes = []
+    lib.ma_mc_spatial_step_field_names.restype = ctypes.c_char_p
+    mirror = [name for name, _ in McSpatialStep._fields_]
+    if mc_spatial_step_native_fields(lib) != mirror or lib.ma_mc_spatial_step_sizeof() != ctypes.sizeof(McSpatialStep):
+        raise RuntimeError(
+            f"McSpatialStep: the Python mirror {mirror} and csrc/mc_spatial.h {mc_spatial_step_native_fields(lib)}"
+            " differ in field names, order or size; rebuild the library"
+        )
+    native = (lib.ma_mc_spatial_max_classes(), lib.ma_mc_spatial_lds_bytes(), lib.ma_mc_spatial_lds_static())
+    if native != (MC_SPATIAL_MAX_C, MC_SPATIAL_LDS_BYTES, MC_SPATIAL_LDS_STATIC):
+        raise RuntimeError(
+            f"csrc/mc_spatial.hip: class cap and LDS gate {native} differ from the Python constants; rebuild the library"
+        )
+
+
+def mc_spatial_step_native_fields(lib: ctypes.CDLL) -> list:
+    """The field names of the native ``McSpatialStep`` in declaration order."""
+    return lib.ma_mc_spatial_step_field_names().decode().rstrip(",").split(",")
 
 
 def bin_step_native_fields(lib: ctypes.CDLL) -> list:
@@ -1935,6 +2022,157 @@ def bin_step_update(
         # histogram accumulates, the suffix/confmat materialization waits for a
         # state read
         curve.__dict__["_hip_lazy_meta"] = (1, T, 0)
+        curve.__dict__["_lazy_dirty"] = True
+    return True
+
+
+# Fused spatial multiclass step (csrc/mc_spatial.hip): (N, C, *spatial) float
+# predictions with an (N, *spatial) target. METRICS_AMD_FUSE_SPATIAL=0 keeps
+# every leader on its own update path, exactly as before (A/B lever, escape
+# hatch and the oracle of the tests). Read when a collection builds its plan.
+FUSE_SPATIAL_ENV = "METRICS_AMD_FUSE_SPATIAL"
+
+# Class cap: the step kernel counts tp/fp/fn in an LDS block [3][C] u32.
+MC_SPATIAL_MAX_C = 256
+# Curve gate: the curve leader rides the step while the block's private
+# histogram [C][T+1][2] u32, the count block and the static part (block record
+# and reduction words, rounded up) fit the 160 KiB of a gfx950 workgroup:
+# 8*C*(T+1) + 12*C + 128 <= 163840 (SP_LDS_BYTES / SP_LDS_STATIC in
+# csrc/mc_spatial.hip), C <= 101 at T = 200. The T float thresholds join them
+# in LDS while 4*T more bytes fit and are read from global memory otherwise;
+# the (C, C) matrix joins while it still fits behind all of that. Above the
+# gate the curve leader updates on its own and the other leaders still fuse.
+MC_SPATIAL_LDS_BYTES = 160 * 1024
+MC_SPATIAL_LDS_STATIC = 128
+
+_MC_SPATIAL_LAYOUT_CACHE: dict = {}
+
+
+def fuse_spatial_enabled() -> bool:
+    return os.environ.get(FUSE_SPATIAL_ENV, "1") != "0"
+
+
+def mc_spatial_curve_rides(num_classes: int, num_thresholds: int) -> bool:
+    """The curve gate of the fused spatial step."""
+    C, T = int(num_classes), int(num_thresholds)
+    return 8 * C * (T + 1) + 12 * C + MC_SPATIAL_LDS_STATIC <= MC_SPATIAL_LDS_BYTES
+
+
+def mc_spatial_max_curve_classes(num_thresholds: int) -> int:
+    """The largest class count with which the curve leader rides at this
+    threshold count (the class cap aside)."""
+    return (MC_SPATIAL_LDS_BYTES - MC_SPATIAL_LDS_STATIC) // (8 * (int(num_thresholds) + 1) + 12)
+
+
+def mc_spatial_layout(N: int, C: int, S: int, dtype_code: int, num_thresholds: int) -> Optional[tuple]:
+    """(pixels per lane of the vector path, 1 if the shape takes it, pixels per
+    wave tile, threads per block, step blocks, tail blocks, dynamic LDS bytes,
+    1 if the (C, C) matrix is kept in LDS, 1 if the thresholds are, wave tiles,
+    tile flag bytes to provide, record words to provide) of a fused spatial
+    step over (N, C, S) predictions of fp32 (``dtype_code`` 0) or bf16 (1) at a
+    16-byte aligned address, None where the kernels do not cover the shape.
+    ``num_thresholds`` 0: no curve leader. Host only."""
+    key = (N, C, S, dtype_code, num_thresholds)
+    if key not in _MC_SPATIAL_LAYOUT_CACHE:
+        out = (_LL * 12)()
+        rc = _lib().ma_mc_spatial_layout(N, C, S, dtype_code, num_thresholds, out)
+        if len(_MC_SPATIAL_LAYOUT_CACHE) > 256:
+            _MC_SPATIAL_LAYOUT_CACHE.clear()
+        _MC_SPATIAL_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _MC_SPATIAL_LAYOUT_CACHE[key]
+
+
+def mc_spatial_step_update(
+    preds: Tensor, target: Tensor, num_classes: int, ignore_index: Optional[int],
+    stat=None, confmat=None, exact=None, curve=None,
+) -> bool:
+    """The whole step of a multiclass collection fed (N, C, *spatial) fp32 /
+    bf16 ``preds`` and an int64 ``target`` (N, *spatial), in ONE native call of
+    two launches that reads both once and transposes nothing: per-class stat
+    counts into the ``stat`` leader's tp/fp/tn/fn, the (C, C) counts into the
+    ``confmat`` leader's state, the exact-match counts into the ``exact``
+    leader's correct/total, and the threshold-curve histogram into the
+    ``curve`` leader's lazy buffer (absent leaders are None). Every buffer
+    lives in the ``__dict__`` of the leader it serves (:func:`owner_buffer`);
+    no allocation, fill or host sync in steady state. Both inputs must be
+    contiguous.
+
+    Returns False without launching anything where the kernels do not cover
+    the shape: the caller lets every leader update on its own.
+    """
+    lib = _lib()
+    dt = _dtype_code(preds)
+    N, C = preds.shape[0], num_classes
+    S = preds.numel() // (N * C) if N else math.prod(preds.shape[2:])
+    dev = preds.device
+    base = stat if stat is not None else confmat if confmat is not None else exact if exact is not None else curve
+    thr, T = None, 0
+    if curve is not None:
+        src = curve.thresholds
+        hit = curve.__dict__.get("_hip_sp_thr")
+        if hit is not None and hit[0] is src:
+            thr = hit[1]
+        else:
+            thr = src.contiguous().float()
+            curve.__dict__["_hip_sp_thr"] = (src, thr)
+        T = thr.numel()
+    lay = mc_spatial_layout(N, C, S, dt, T)
+    if lay is None:
+        return False
+    if curve is not None:
+        flush_if_b0_pending(curve)  # a one-pass step over 2-D batches wrote last: complete its histogram first
+    tensors = McSpatialStepTensors(
+        counts=owner_buffer(base, "_hip_sp_counts", (3 * C,), torch.long, dev),
+        records=owner_buffer(base, "_hip_sp_records", (lay[11],), torch.int32, dev),
+        tp=stat.tp if stat is not None else None,
+        fp=stat.fp if stat is not None else None,
+        tn=stat.tn if stat is not None else None,
+        fn=stat.fn if stat is not None else None,
+        confmat=confmat.confmat if confmat is not None else None,
+        correct=exact.correct if exact is not None else None,
+        total=exact.total if exact is not None else None,
+        rowbad=owner_buffer(exact, "_hip_sp_rowbad", (max(N, 1),), torch.int32, dev, grow=True)
+        if exact is not None else None,
+    )
+    if curve is not None:
+        tensors = tensors._replace(
+            thresholds=thr,
+            hist=_pooled_hist(C, T, dev, curve),
+            epoch_buf=_epoch_buf(dev, curve),
+            rowstats=_rowstats_buf(curve, max(N * S, 1), dev),
+            tile_flags=owner_buffer(curve, "_hip_sp_tile_flags", (max(lay[10], 1),), torch.uint8, dev, grow=True),
+        )
+    # the record holds the addresses of everything that stays the same from
+    # step to step; reset() and a move to another device replace state tensors
+    # and the next step rebuilds it (the identity rule of _NativePlan.fits)
+    scalars = (C, ignore_index, T)
+    kept = base.__dict__.get("_hip_sp_rec")
+    if kept is not None and kept.scalars == scalars and all(map(operator.is_, kept.tensors, tensors)):
+        rec = kept.rec
+    else:
+        for name, shape in (("tp", (C,)), ("fp", (C,)), ("tn", (C,)), ("fn", (C,)), ("confmat", (C, C)),
+                            ("correct", (1,)), ("total", (1,))):
+            x = getattr(tensors, name)
+            if x is not None and not (
+                x.is_contiguous() and x.dtype == torch.long and x.device == dev and tuple(x.shape) == shape
+            ):
+                return False
+        rec = mc_spatial_step(C, ignore_index, tensors, _uniform_params(thr) if curve is not None else (0, 0.0, 1.0))
+        base.__dict__["_hip_sp_rec"] = _MlStepRecord(tensors, scalars, rec)
+    rc = lib.ma_mc_spatial_step(_stream(), rec, preds.data_ptr(), dt, target.data_ptr(), N, S)
+    if rc == -103:
+        return False  # nothing was launched
+    _check(rc, "ma_mc_spatial_step")
+    # the raw-pointer writes of the step, for the version-keyed caches (the
+    # same states mc_step_mark_mutated notes)
+    if tensors.confmat is not None:
+        _mark_kernel_mutated(tensors.confmat)
+    if tensors.tp is not None:
+        _mark_kernel_mutated(tensors.tp)
+    if curve is not None:
+        # same lazy protocol as curve_hist_into_confmat: the histogram
+        # accumulates, the suffix/confmat materialization waits for a state read
+        curve.__dict__["_hip_lazy_meta"] = (C, T, 1)
         curve.__dict__["_lazy_dirty"] = True
     return True
 
