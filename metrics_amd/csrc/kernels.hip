@@ -947,7 +947,8 @@ __global__ void __launch_bounds__(256) k_err_reduce_partial(
                 acc[0] += xd; acc[1] += xd * xd; acc[2] += yd; acc[3] += yd * yd; acc[4] += xd * yd;
                 acc[5] += 1.0;
                 break;
-            case 5: { double d = xd - yd; acc[0] += d + log1p(exp(-2.0 * d)) - 0.6931471805599453; } break;
+            // log cosh d = |d| + log1p(exp(-2|d|)) - ln 2: exp never overflows
+            case 5: { double d = fabs(xd - yd); acc[0] += d + log1p(exp(-2.0 * d)) - 0.6931471805599453; } break;
         }
     }
     // block tree-reduce each accumulator

@@ -121,12 +121,21 @@ __global__ void __launch_bounds__(NTHREADS) k_ssim2d_fused(
             m_tt += w * filt[3 * row_elems + r];
             m_pt += w * filt[4 * row_elems + r];
         }
-        const float mu_p2 = mu_p * mu_p;
-        const float mu_t2 = mu_t * mu_t;
-        const float mu_pt = mu_p * mu_t;
-        const float s_p = fmaxf(m_pp - mu_p2, 0.f);
-        const float s_t = fmaxf(m_tt - mu_t2, 0.f);
-        const float s_pt = m_pt - mu_pt;
+        // rounded products, never contracted into the subtractions: an fma would
+        // subtract the exact mu^2 from the rounded moment and leave that moment's
+        // rounding error as variance (a 1-pixel window has variance 0, and gets
+        // exactly 0 only this way). __fmul_rn is a plain product here and would
+        // be contracted all the same, so contraction is off for this block.
+        float mu_p2, mu_t2, mu_pt, s_p, s_t, s_pt;
+        {
+#pragma clang fp contract(off)
+            mu_p2 = mu_p * mu_p;
+            mu_t2 = mu_t * mu_t;
+            mu_pt = mu_p * mu_t;
+            s_p = fmaxf(m_pp - mu_p2, 0.f);
+            s_t = fmaxf(m_tt - mu_t2, 0.f);
+            s_pt = m_pt - mu_pt;
+        }
         const float upper = 2.f * s_pt + c2;
         const float lower = s_p + s_t + c2;
         const float ssim = ((2.f * mu_pt + c1) * upper) / ((mu_p2 + mu_t2 + c1) * lower);
@@ -166,6 +175,9 @@ extern "C" int ma_ssim2d_fused(
     int want_cs, int crop_h, int crop_w,
     uint64_t sum_sim_u, uint64_t sum_cs_u) {
     hipStream_t stream = (hipStream_t)stream_u;
+    // grid.y and grid.z hold at most 65535 blocks: more planes (or tile rows)
+    // than that take the torch path, like a window past the LDS tile
+    if (B * C > 65535 || (H + TS - 1) / TS > 65535) return 9001;
     dim3 grid((W + TS - 1) / TS, (H + TS - 1) / TS, B * C);
     const int patch_w = TS + 2 * rw;
     const int patch_h = TS + 2 * rh;

@@ -152,7 +152,12 @@ def _ssim_compute(
         raise ValueError(f"Expected `sigma` to have positive number. Got {sigma}.")
 
     if data_range is None:
-        data_range_t = max(preds.max() - preds.min(), target.max() - target.min())
+        if preds.dtype in (torch.bfloat16, torch.float16):
+            # the difference of two 8- or 11-bit values is not one: take it in fp32
+            data_range_t = max(preds.max().float() - preds.min().float(),
+                               target.max().float() - target.min().float())
+        else:
+            data_range_t = max(preds.max() - preds.min(), target.max() - target.min())
     elif isinstance(data_range, tuple):
         preds = torch.clamp(preds, min=data_range[0], max=data_range[1])
         target = torch.clamp(target, min=data_range[0], max=data_range[1])

@@ -18,7 +18,8 @@ def _unsqueeze_tensors(preds: Tensor, target: Tensor) -> Tuple[Tensor, Tensor]:
 
 def _log_cosh_error_update(preds: Tensor, target: Tensor, num_outputs: int) -> Tuple[Tensor, int]:
     _check_same_shape(preds, target)
-    if num_outputs == 1 and preds.is_cuda and preds.dtype in (torch.float32, torch.bfloat16):
+    if (num_outputs == 1 and preds.is_cuda and preds.dtype in (torch.float32, torch.bfloat16)
+            and target.dtype == preds.dtype):
         p = preds.reshape(-1)
         t = target.reshape(-1)
         return ops.err_reduce_sum(p, t, "logcosh")[0].float(), t.numel()

@@ -9,6 +9,7 @@ the native path must be the one that runs, never a silent eager fallback.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -179,8 +180,10 @@ def err_reduce_sum(x: Tensor, y: Tensor, op: str, eps: float = 1.17e-6) -> Tenso
     if op == "sq_log_err":
         return (torch.log1p(xd) - torch.log1p(yd)).pow(2).sum().reshape(1)
     if op == "logcosh":
-        d = xd - yd
-        return (d + torch.nn.functional.softplus(-2 * d) - torch.log(torch.tensor(2.0))).sum().reshape(1)
+        # log cosh d = |d| + log1p(exp(-2|d|)) - ln 2, the kernel's formula: symmetric,
+        # no overflow, ln 2 in fp64 (softplus goes linear past 20, 2e-9 off)
+        d = (xd - yd).abs()
+        return (d + torch.log1p(torch.exp(-2 * d)) - math.log(2.0)).sum().reshape(1)
     if op == "moments":
         return torch.stack(
             [xd.sum(), (xd * xd).sum(), yd.sum(), (yd * yd).sum(), (xd * yd).sum(), torch.tensor(float(xd.numel()))]

@@ -1002,6 +1002,8 @@ def err_reduce(x: Tensor, y: Tensor, op: str, eps: float = 1.17e-6) -> Tensor:
     """Deterministic fused elementwise-error reduction; returns fp64 sums (n_out,)."""
     lib = _lib()
     op_id, n_out = _ERR_OPS[op]
+    if y.dtype != x.dtype or y.numel() != x.numel():  # the kernel reads both as x's type and length
+        raise TypeError(f"err_reduce needs x and y of one dtype and size, got {x.dtype}[{x.numel()}] and {y.dtype}[{y.numel()}]")
     x = x.contiguous()
     y = y.contiguous()
     N = x.numel()
@@ -1027,6 +1029,10 @@ def err_reduce(x: Tensor, y: Tensor, op: str, eps: float = 1.17e-6) -> Tensor:
 
 
 _CALIB_SCALE = 8589934592.0  # 2^33, matches csrc/kernels2.hip
+
+
+class CalibLdsOverflow(RuntimeError):
+    """More bins than the LDS histogram holds (2048); caller falls back."""
 
 
 def calib_bins(conf: Tensor, acc: Tensor, bounds: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
@@ -1055,7 +1061,7 @@ def calib_bins(conf: Tensor, acc: Tensor, bounds: Tensor) -> Tuple[Tensor, Tenso
         out.data_ptr(),
     )
     if rc == 9001:
-        raise RuntimeError("calibration bin count exceeds the LDS budget")
+        raise CalibLdsOverflow("calibration bin count exceeds the LDS budget")
     _check(rc, "ma_calib_bins")
     count = out[0].float()
     conf_sum = out[1].double().div_(_CALIB_SCALE).float()
@@ -1102,7 +1108,8 @@ def mc_topk_stat(
 
 
 class SsimLdsOverflow(RuntimeError):
-    """Window too large for the one-kernel LDS tiling; caller falls back."""
+    """Window too large for the one-kernel LDS tiling, or more than 65535
+    planes (the grid's z limit); caller falls back."""
 
 
 def ssim2d_fused(
@@ -1153,7 +1160,8 @@ def ssim2d_fused(
         sum_cs.data_ptr() if sum_cs is not None else 0,
     )
     if rc == 9001:
-        raise SsimLdsOverflow(f"window radius ({rh},{rw}) exceeds the LDS tile budget")
+        raise SsimLdsOverflow(
+            f"window radius ({rh},{rw}) exceeds the LDS tile budget, or {B * C} planes exceed the grid")
     _check(rc, "ma_ssim2d_fused")
     return sum_sim, sum_cs
 
