@@ -19,19 +19,32 @@ CSRC = Path(__file__).resolve().parent
 LIBDIR = CSRC.parent / "_lib"
 LIBNAME = "libmetrics_hip.so"
 ARCH = os.environ.get("METRICS_AMD_ARCH", "gfx950")
+# Sources compiled with flags of their own. lm_nll.hip is built without the
+# packed fp32 instructions (v_pk_add/mul/fma_f32): its folds are scalar per
+# lane, and nothing in it may be paired up by the compiler.
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+OWN_FLAGS = {"lm_nll.hip": NO_PACKED_FP32}
 
 
 def build(verbose: bool = True) -> Path:
     """Compile csrc/*.hip (gfx950) and csrc/*.cpp (host) into metrics_amd/_lib/."""
     LIBDIR.mkdir(exist_ok=True)
     out = LIBDIR / LIBNAME
-    srcs = sorted(str(p) for p in CSRC.glob("*.hip"))
+    base = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC"]
+    srcs = []
+    for p in sorted(CSRC.glob("*.hip")):
+        if p.name not in OWN_FLAGS:
+            srcs.append(str(p))
+            continue
+        # a file with flags of its own becomes an object first (under _lib/, untracked)
+        obj = LIBDIR / (p.stem + ".o")
+        cmd = [*base, *OWN_FLAGS[p.name], "-c", str(p), "-o", str(obj)]
+        if verbose:
+            print("+", " ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
+        srcs.append(f"-Wl,{obj}")  # straight to the linker: hipcc reads every bare input as HIP source
     cmd = [
-        "hipcc",
-        f"--offload-arch={ARCH}",
-        "-O3",
-        "-std=c++17",
-        "-fPIC",
+        *base,
         "-shared",
         *srcs,
         "-o",

@@ -66,8 +66,7 @@ def squad(preds, target) -> Dict[str, Tensor]:
 
 
 # -------------------------------------------------------------------- Perplexity
-def _perplexity_update(preds: Tensor, target: Tensor, ignore_index: Optional[int] = None) -> Tuple[Tensor, Tensor]:
-    """Accumulate total negative log likelihood + token count from logits."""
+def _perplexity_check_shapes(preds: Tensor, target: Tensor) -> None:
     if preds.ndim != 3:
         raise ValueError(f"Input tensor `preds` is expected to have 3 dimensions, [batch_size, seq_len, vocab_size], but got {preds.ndim}.")
     if target.ndim != 2:
@@ -77,6 +76,23 @@ def _perplexity_update(preds: Tensor, target: Tensor, ignore_index: Optional[int
             "Input tensors `preds` and `target` are expected to have equaling first two dimensions,"
             f" [batch_size, seq_len], but got {preds.shape[:2]} and {target.shape}."
         )
+
+
+def _perplexity_update(preds: Tensor, target: Tensor, ignore_index: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """Accumulate total negative log likelihood + token count from logits.
+
+    GPU: one pass of the NLL kernel (csrc/lm_nll.hip) over the logits as they
+    lie, strided views included, where ``ops/_hip.py`` ``lm_nll_into`` covers
+    the call; no host sync. The torch chain below runs everywhere else, and
+    wherever a graph must be carried (``preds.requires_grad`` with grad on).
+    """
+    _perplexity_check_shapes(preds, target)
+    if preds.is_cuda:
+        from metrics_amd.ops import _hip
+
+        sums = _hip.lm_nll_sums(preds, target, ignore_index)
+        if sums is not None:
+            return sums[0].to(preds.dtype), sums[1].long()
 
     probs = torch.nn.functional.log_softmax(preds.reshape(-1, preds.shape[-1]).double(), dim=1)
     target_flat = target.reshape(-1)

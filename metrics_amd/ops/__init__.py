@@ -125,6 +125,14 @@ def multilabel_ranking_sums(
     return _hip.ml_ranking_sums(scores, target, ignore_index, want)
 
 
+def perplexity_sums(preds: Tensor, target: Tensor, ignore_index: Optional[int] = None) -> Optional[Tensor]:
+    """GPU negative-log-likelihood sums of (B, T, V) logits against (B, T) int64
+    targets: a (2,) fp64 tensor [total, kept rows], before the rounding to the
+    input dtype that ``Perplexity`` applies. None where the kernel does not
+    cover the call (``ops/_hip.py`` ``lm_nll_into``)."""
+    return _hip.lm_nll_sums(preds, target, ignore_index)
+
+
 def binary_curve_confmat(
     preds: Tensor, target: Tensor, thresholds: Tensor, ignore_index: Optional[int] = None
 ) -> Tensor:

@@ -287,6 +287,8 @@ _SIGNATURES = {
     "ma_ml_step_sizeof": [],
     "ma_ml_rank": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _I, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64],
     "ma_ml_rank_layout": [_LL, _LL, ctypes.POINTER(_LL)],
+    "ma_lm_nll": [_U64, _U64, _I, _U64, _LL, _LL, _LL, _LL, _LL, _LL, _LL, _LL, _I, _U64, _U64, _U64, _U64],
+    "ma_lm_nll_layout": [_LL, _LL, _I, ctypes.POINTER(_LL)],
     "ma_mc_stat_logits": [_U64, _STEP_P, _U64, _I, _U64, _LL, _U64],
     "ma_mc_stat_topk_covers": [_LL],
     "ma_mc_stat_labels": [_U64, _STEP_P, _U64, _U64, _LL],
@@ -2288,6 +2290,116 @@ def ml_ranking_sums(preds: Tensor, target: Tensor, ignore_index: Optional[int], 
     pairs = [(out[i, 0], out[i, 1]) if want & bit else None
              for i, bit in enumerate((RANK_WANT_COVERAGE, RANK_WANT_LRAP, RANK_WANT_LOSS))]
     if not ml_ranking_into(preds, target, ignore_index, *pairs):
+        return None
+    return out
+
+
+# Language-model NLL sums behind Perplexity (csrc/lm_nll.hip).
+# METRICS_AMD_PERPLEXITY_KERNEL=0 keeps the torch chain of
+# functional/text/misc.py everywhere (A/B lever, escape hatch). Read at every
+# call.
+PERPLEXITY_KERNEL_ENV = "METRICS_AMD_PERPLEXITY_KERNEL"
+
+# dtype codes of this kernel alone: it reads fp16 natively (code 2)
+_LM_NLL_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+_LM_NLL_FUNCTIONAL_OWNERS: dict = {}
+
+
+class _LmNllOwner:
+    """Holds the slab of the functional form, one per device."""
+
+
+def perplexity_kernel_enabled() -> bool:
+    return os.environ.get(PERPLEXITY_KERNEL_ENV, "1") != "0"
+
+
+class LmNllLayout(NamedTuple):
+    """What ``ma_lm_nll_layout`` reports for (rows, V, dtype)."""
+
+    mapping: int  # 1 group per row, 2 wave per row, 3 block per row
+    lanes_per_row: int
+    rows_per_wave: int
+    rows_per_block: int  # per pass of the grid-stride loop
+    grid: int
+    slab_entries: int  # of 16 bytes each
+    last_group_v: int  # B1: the last V of mapping 1
+    last_wave_v: int  # B2: the last V of mapping 2 at this row count
+    max_v: int
+    block_rows: int  # mapping 3 only below this many rows
+
+
+def lm_nll_layout(rows: int, vocab: int, dtype=torch.float32) -> Optional[LmNllLayout]:
+    """The mapping, grid and mapping boundaries of an NLL call, None where the
+    kernel does not cover the shape or dtype. Host only; not cached, because the
+    grid follows the ``MA_LM_NLL_GRID`` knob."""
+    code = _LM_NLL_DTYPES.get(dtype)
+    if code is None:
+        return None
+    out = (_LL * 10)()
+    rc = _lib().ma_lm_nll_layout(rows, vocab, code, out)
+    return LmNllLayout(*out) if rc == 0 else None
+
+
+def lm_nll_into(
+    preds: Tensor, target: Tensor, ignore_index: Optional[int],
+    total: Optional[Tensor], count: Optional[Tensor], owner=None, _sums: Optional[Tensor] = None,
+) -> bool:
+    """Total negative log likelihood and kept-row count of (B, T, V) logits
+    against (B, T) int64 targets in ONE native call of two launches, added in
+    place into the one-element fp32 tensors ``total`` (after rounding to the
+    dtype of ``preds``, as the torch update does) and ``count``. Strided views
+    are read in place; only ``preds.stride(-1) == 1`` is required. The slab
+    lives in the ``__dict__`` of ``owner`` (:func:`owner_buffer`); no
+    allocation, fill or host sync in steady state.
+
+    Returns False without launching anything where the kernel does not cover
+    the call: switch off, CPU, another dtype, a graph to carry, a shape outside
+    the layout, or states of another kind. The caller runs the torch chain.
+    """
+    if not (perplexity_kernel_enabled() and preds.is_cuda and preds.ndim == 3 and target.ndim == 2):
+        return False
+    code = _LM_NLL_DTYPES.get(preds.dtype)
+    dev = preds.device
+    if (code is None or target.dtype != torch.int64 or target.device != dev or preds.shape[:2] != target.shape
+            or preds.stride(-1) != 1 or preds.numel() == 0
+            or (torch.is_grad_enabled() and preds.requires_grad)):
+        return False
+    if _sums is None and not _rank_state_ok((total, count), dev):
+        return False
+    if owner is None:
+        owner = _LM_NLL_FUNCTIONAL_OWNERS.get(dev)
+        if owner is None:
+            owner = _LM_NLL_FUNCTIONAL_OWNERS[dev] = _LmNllOwner()
+    lib = _lib()
+    slab = owner.__dict__.get("_hip_lm_nll_slab")
+    if slab is None or slab.device != dev:
+        out = (_LL * 10)()
+        lib.ma_lm_nll_layout(1, 1, 0, out)
+        slab = owner_buffer(owner, "_hip_lm_nll_slab", (out[5] * 2,), torch.float64, dev, zero=False)
+    B, T, V = preds.shape
+    rc = lib.ma_lm_nll(
+        _stream(), preds.data_ptr(), code, target.data_ptr(), B, T, V,
+        preds.stride(0), preds.stride(1), target.stride(0), target.stride(1),
+        ignore_index if ignore_index is not None else 0, int(ignore_index is not None),
+        slab.data_ptr(),
+        total.data_ptr() if _sums is None else 0, count.data_ptr() if _sums is None else 0,
+        _sums.data_ptr() if _sums is not None else 0,
+    )
+    if rc == -103:
+        return False  # nothing was launched
+    _check(rc, "ma_lm_nll")
+    return True
+
+
+def lm_nll_sums(preds: Tensor, target: Tensor, ignore_index: Optional[int]) -> Optional[Tensor]:
+    """Functional form: a fresh (2,) fp64 tensor [total, count], the total
+    before any rounding to the dtype of ``preds``. None where
+    :func:`lm_nll_into` does not cover the call."""
+    if not preds.is_cuda:
+        return None
+    out = torch.empty(2, dtype=torch.float64, device=preds.device)
+    if not lm_nll_into(preds, target, ignore_index, None, None, _sums=out):
         return None
     return out
 
