@@ -325,6 +325,9 @@ _SIGNATURES = {
     "ma_mc_clf_curve": [_U64, _U64, _U64, _LL, _LL, _I, _U64, ctypes.c_ulonglong, _U64, _U64, _U64, _U64],
     "ma_retrieval_sort_scratch_bytes": [_LL, ctypes.POINTER(ctypes.c_ulonglong)],
     "ma_retrieval_sort": [_U64, _U64, _U64, _LL, _U64, ctypes.c_ulonglong, _U64, _U64],
+    "ma_retrieval_scores_layout": [_LL, _I, ctypes.POINTER(_LL)],
+    "ma_retrieval_scores": [_U64, _U64, _U64, _U64, _I, _LL, _I, _I, _I, _I, _I, _I, _I, _I, _U64,
+                            ctypes.c_ulonglong, _U64, _U64, _U64, _U64],
     "ma_mc_topk_stat": [_U64, _U64, _I, _U64, _LL, _LL, _I, _LL, _I, _U64, _U64, _U64, _U64],
 }
 
@@ -995,6 +998,144 @@ def retrieval_sort(indexes: Tensor, preds: Tensor) -> Tuple[Tensor, Tensor]:
     )
     _check(rc, "ma_retrieval_sort")
     return order.long(), by_index.long()
+
+
+# Retrieval scoring (csrc/retrieval_score.hip): every query of a compute() in
+# one segmented pass. METRICS_AMD_RETRIEVAL_KERNEL=0 keeps the torch path of
+# retrieval/base.py and the per-query loops everywhere, exactly as before (A/B
+# lever and escape hatch). Read at every call.
+RETRIEVAL_KERNEL_ENV = "METRICS_AMD_RETRIEVAL_KERNEL"
+
+# A query longer than this is owned by a whole block instead of a group of
+# lanes (RETR_BLOCK_MIN in csrc/retrieval_score.hip, which gives the reason).
+RETRIEVAL_BLOCK_MIN = 2048
+
+# Gate: where the indexes span so few values that the MEAN query is longer than
+# this, the path before the kernel runs. One block walks a long query at about
+# 2.4 ns per element (2.7 ms for one query of 1 M elements, against 1.0 - 2.7 ms
+# of the torch path: docs/ROADMAP.md), so a handful of huge queries is the one
+# shape measured where the kernel loses. n / (max index - min index + 1) bounds
+# the mean from below with what the range check already brought to the host.
+RETRIEVAL_MAX_MEAN_QUERY = 2**18
+
+# No PR curve above this many cum_rel entries (1 GiB of int32): the loop runs.
+RETRIEVAL_CURVE_MAX_ENTRIES = 2**28
+
+RETR_WANT_AP, RETR_WANT_NDCG, RETR_WANT_AUROC, RETR_WANT_RPREC, RETR_WANT_CURVE = 1, 2, 4, 8, 16
+# kernel score name -> (metric id of the tail, what the score kernel must produce)
+RETRIEVAL_SCORES = {
+    "map": (0, RETR_WANT_AP), "mrr": (1, 0), "precision": (2, 0), "recall": (3, 0), "hit_rate": (4, 0),
+    "fall_out": (5, 0), "ndcg": (6, RETR_WANT_NDCG), "r_precision": (7, RETR_WANT_RPREC),
+    "auroc": (8, RETR_WANT_AUROC), "curve": (9, RETR_WANT_CURVE),
+}
+_RETR_ACTIONS = {"neg": 0, "pos": 1, "skip": 2, "error": 3}
+_RETR_AGGS = {"mean": 0, "min": 1, "max": 2}
+_RETR_LAYOUT_CACHE: dict = {}
+_RETR_FUNCTIONAL_OWNERS: dict = {}
+
+
+class _RetrievalOwner:
+    """Holds the scratch of calls without an owner, one per device."""
+
+
+class RetrievalScores(NamedTuple):
+    """What one scoring call left on the device. ``value`` is the aggregated
+    scalar (fresh, one fp32), ``scores`` / ``empty`` the per-query score and
+    empty flag in the owner's n-capacity buffers (the first G entries count),
+    ``header`` the int32 view [G, largest query, smallest query, empty
+    queries, kept queries, ...]; the two extents only in curve mode."""
+
+    value: Tensor
+    scores: Tensor
+    empty: Tensor
+    header: Tensor
+    scratch: Tensor
+    records_offset: int
+
+
+def retrieval_kernel_enabled() -> bool:
+    return os.environ.get(RETRIEVAL_KERNEL_ENV, "1") != "0"
+
+
+def retrieval_kernel_covers(n: int, lo: int, hi: int) -> bool:
+    """Whether compute() over ``n`` elements with indexes in [lo, hi] takes the
+    kernel: the switch is on, the indexes fit the composite key, and the mean
+    query is not longer than ``RETRIEVAL_MAX_MEAN_QUERY``."""
+    return retrieval_kernel_enabled() and lo >= 0 and hi < 2**31 and n // (hi - lo + 1) <= RETRIEVAL_MAX_MEAN_QUERY
+
+
+def retrieval_scores_layout(n: int, ndcg: bool = False) -> Optional[tuple]:
+    """(scratch bytes, offset of the records, bytes of a record, longest query
+    of the group mapping, blocks of the group launch, of the block launch, of
+    the tail) for a call over ``n`` elements; None where n is not covered."""
+    key = (n, bool(ndcg))
+    if key not in _RETR_LAYOUT_CACHE:
+        out = (_LL * 7)()
+        rc = _lib().ma_retrieval_scores_layout(n, int(ndcg), out)
+        if rc not in (0, -103):
+            _check(rc, "ma_retrieval_scores_layout")
+        if len(_RETR_LAYOUT_CACHE) > 256:
+            _RETR_LAYOUT_CACHE.clear()
+        _RETR_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _RETR_LAYOUT_CACHE[key]
+
+
+def retrieval_scores(
+    indexes: Tensor, preds: Tensor, target: Tensor, metric: str,
+    top_k: Optional[int] = None, adaptive_k: bool = False, action: str = "neg", aggregation="mean",
+    owner=None, phases: int = 3, max_k: int = 0, cum_rel: Optional[Tensor] = None,
+) -> Optional[RetrievalScores]:
+    """Score every query of (indexes, preds, target) in ONE native call on the
+    current stream: sort, query heads, ``k_retrieval_score``, tail. ``metric``
+    names an entry of ``RETRIEVAL_SCORES``; ``aggregation`` other than mean /
+    min / max leaves ``value`` unwritten (the caller takes ``scores``).
+    Indexes must lie in [0, 2^31). The scratch lives in the ``__dict__`` of
+    ``owner``. ``phases``: 1 stops after the query heads (the header then
+    holds G and, for "curve", the extents), 2 continues such a call, 3 both.
+
+    No host sync. Returns None without launching anything where the kernel
+    does not cover the call: the caller runs the torch path.
+    """
+    lib = _lib()
+    mid, want = RETRIEVAL_SCORES[metric]
+    n = preds.numel()
+    dev = preds.device
+    lay = retrieval_scores_layout(n, bool(want & RETR_WANT_NDCG)) if n else None
+    if lay is None or top_k is not None and top_k >= 2**31:
+        return None
+    indexes = indexes.contiguous()
+    preds = preds.float().contiguous()
+    target = (target.float() if target.is_floating_point() else target.long()).contiguous()
+    if owner is None:
+        owner = _RETR_FUNCTIONAL_OWNERS.get(dev)
+        if owner is None:
+            owner = _RETR_FUNCTIONAL_OWNERS[dev] = _RetrievalOwner()
+    scratch = owner_buffer(owner, "_hip_retr_scratch", (lay[0],), torch.uint8, dev, zero=False, grow=True)
+    scores = owner_buffer(owner, "_hip_retr_scores", (n,), torch.float32, dev, zero=False, grow=True)
+    empty = owner_buffer(owner, "_hip_retr_empty", (n,), torch.uint8, dev, zero=False, grow=True)
+    value = torch.empty(1, dtype=torch.float32, device=dev)
+    rc = lib.ma_retrieval_scores(
+        _stream(), indexes.data_ptr(), preds.data_ptr(), target.data_ptr(), int(target.dtype == torch.long),
+        n, top_k or 0, max_k, want, mid, int(adaptive_k), _RETR_ACTIONS[action], _RETR_AGGS.get(aggregation, 3),
+        phases, scratch.data_ptr(), scratch.numel(), cum_rel.data_ptr() if cum_rel is not None else 0,
+        scores.data_ptr(), empty.data_ptr(), value.data_ptr(),
+    )
+    if rc == -103:
+        return None  # nothing was launched
+    _check(rc, "ma_retrieval_scores")
+    return RetrievalScores(value, scores, empty, scratch[:32].view(torch.int32), scratch, lay[1])
+
+
+def retrieval_records(res: RetrievalScores, G: int) -> dict:
+    """The per-query records of a call as tensors (copies), by field name."""
+    raw = res.scratch[res.records_offset:res.records_offset + G * 72].view(G, 72)
+    ints = raw[:, :32].contiguous().view(torch.int32)
+    dbl = raw[:, 40:].contiguous().view(torch.float64)
+    out = {name: ints[:, i] for i, name in enumerate(
+        ("count", "npos", "nneg", "hits_k", "neg_hits_k", "first_pos", "hits_r"))}
+    out["u"] = raw[:, 32:40].contiguous().view(torch.int64)[:, 0]
+    out.update({name: dbl[:, i] for i, name in enumerate(("tsum", "ap", "dcg", "idcg"))})
+    return out
 
 
 _ERR_OPS = {"sq_err": (0, 1), "abs_err": (1, 1), "ape": (2, 1), "sq_log_err": (3, 1), "moments": (4, 6), "logcosh": (5, 1)}

@@ -149,6 +149,48 @@ class RetrievalMetric(Metric, ABC):
 
     # batched path: which per-query condition triggers empty_target_action
     _empty_on_negatives: bool = False
+    # the entry of ``_hip.RETRIEVAL_SCORES`` that scores this metric in the
+    # segmented HIP pass (csrc/retrieval_score.hip); None: no kernel score
+    _kernel_score: Optional[str] = None
+
+    def _kernel_score_name(self) -> Optional[str]:
+        return self._kernel_score
+
+    def _kernel_inputs_ok(self, indexes: Tensor) -> bool:
+        """CUDA inputs, the kernel switched on, indexes within [0, 2^31), queries not huge."""
+        if not (indexes.is_cuda and indexes.numel()):
+            return False
+        from metrics_amd.ops import _hip
+
+        if not _hip.retrieval_kernel_enabled():
+            return False
+        lo, hi = torch.aminmax(indexes)
+        lo, hi = torch.stack((lo, hi)).tolist()  # the one sync of this path
+        return _hip.retrieval_kernel_covers(indexes.numel(), lo, hi)
+
+    def _kernel_compute(self, indexes: Tensor, preds: Tensor, target: Tensor, name: str) -> Optional[Tensor]:
+        """compute() through the segmented HIP pass; None where it does not cover the call."""
+        from metrics_amd.ops import _hip
+
+        res = _hip.retrieval_scores(
+            indexes, preds, target, name, top_k=getattr(self, "top_k", None),
+            adaptive_k=getattr(self, "adaptive_k", False), action=self.empty_target_action,
+            aggregation=self.aggregation, owner=self,
+        )
+        if res is None:
+            return None
+        if self.aggregation in ("mean", "min", "max") and self.empty_target_action != "error":
+            return res.value[0].to(preds.dtype)
+        G, _, _, n_empty, _ = res.header[:5].tolist()
+        if n_empty and self.empty_target_action == "error":
+            kind = "negative" if self._empty_on_negatives else "positive"
+            raise ValueError(f"`compute` method was provided with a query with no {kind} target.")
+        scores = res.scores[:G].clone()
+        if n_empty and self.empty_target_action == "skip":
+            scores = scores[res.empty[:G] == 0]
+        if not scores.numel():
+            return torch.tensor(0.0).to(preds)
+        return _retrieval_aggregate(scores, self.aggregation).to(preds.dtype)
 
     def compute(self) -> Tensor:
         """Group by query index and average the per-query metric.
@@ -161,6 +203,12 @@ class RetrievalMetric(Metric, ABC):
         indexes = dim_zero_cat(self.indexes)
         preds = dim_zero_cat(self.preds)
         target = dim_zero_cat(self.target)
+
+        name = self._kernel_score_name()
+        if name is not None and self._kernel_inputs_ok(indexes):
+            out = self._kernel_compute(indexes, preds, target, name)
+            if out is not None:
+                return out
 
         grouped = _group_by_query(indexes, preds, target)
         scores = self._batched_scores(grouped)

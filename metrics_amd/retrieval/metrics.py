@@ -45,6 +45,8 @@ class _TopKRetrievalMetric(RetrievalMetric):
 class RetrievalMAP(_TopKRetrievalMetric):
     """Mean average precision."""
 
+    _kernel_score = "map"
+
     def _metric(self, preds: Tensor, target: Tensor) -> Tensor:
         return retrieval_average_precision(preds, target, top_k=self.top_k)
 
@@ -63,6 +65,8 @@ class RetrievalMAP(_TopKRetrievalMetric):
 class RetrievalMRR(_TopKRetrievalMetric):
     """Mean reciprocal rank."""
 
+    _kernel_score = "mrr"
+
     def _metric(self, preds: Tensor, target: Tensor) -> Tensor:
         return retrieval_reciprocal_rank(preds, target, top_k=self.top_k)
 
@@ -77,6 +81,8 @@ class RetrievalMRR(_TopKRetrievalMetric):
 
 class RetrievalPrecision(_TopKRetrievalMetric):
     """Precision@k."""
+
+    _kernel_score = "precision"
 
     def __init__(self, empty_target_action: str = "neg", ignore_index: Optional[int] = None,
                  top_k: Optional[int] = None, adaptive_k: bool = False, aggregation="mean", **kwargs: Any) -> None:
@@ -103,6 +109,8 @@ class RetrievalPrecision(_TopKRetrievalMetric):
 class RetrievalRecall(_TopKRetrievalMetric):
     """Recall@k."""
 
+    _kernel_score = "recall"
+
     def _metric(self, preds: Tensor, target: Tensor) -> Tensor:
         return retrieval_recall(preds, target, top_k=self.top_k)
 
@@ -113,6 +121,8 @@ class RetrievalRecall(_TopKRetrievalMetric):
 
 class RetrievalHitRate(_TopKRetrievalMetric):
     """Hit rate@k."""
+
+    _kernel_score = "hit_rate"
 
     def _metric(self, preds: Tensor, target: Tensor) -> Tensor:
         return retrieval_hit_rate(preds, target, top_k=self.top_k)
@@ -127,6 +137,7 @@ class RetrievalFallOut(_TopKRetrievalMetric):
 
     higher_is_better = False
     _empty_on_negatives = True
+    _kernel_score = "fall_out"
 
     def __init__(self, empty_target_action: str = "pos", ignore_index: Optional[int] = None,
                  top_k: Optional[int] = None, aggregation="mean", **kwargs: Any) -> None:
@@ -144,6 +155,8 @@ class RetrievalFallOut(_TopKRetrievalMetric):
 
 class RetrievalNormalizedDCG(_TopKRetrievalMetric):
     """Normalized DCG (graded relevance allowed)."""
+
+    _kernel_score = "ndcg"
 
     def __init__(self, empty_target_action: str = "neg", ignore_index: Optional[int] = None,
                  top_k: Optional[int] = None, aggregation="mean", **kwargs: Any) -> None:
@@ -169,6 +182,8 @@ class RetrievalNormalizedDCG(_TopKRetrievalMetric):
 class RetrievalRPrecision(RetrievalMetric):
     """R-precision."""
 
+    _kernel_score = "r_precision"
+
     def _metric(self, preds: Tensor, target: Tensor) -> Tensor:
         return retrieval_r_precision(preds, target)
 
@@ -185,6 +200,10 @@ class RetrievalAUROC(_TopKRetrievalMetric):
                  top_k: Optional[int] = None, max_fpr: Optional[float] = None, aggregation="mean", **kwargs: Any) -> None:
         super().__init__(empty_target_action, ignore_index, top_k, aggregation=aggregation, **kwargs)
         self.max_fpr = max_fpr
+
+    def _kernel_score_name(self) -> Optional[str]:
+        # the kernel's Mann-Whitney count is the whole curve: a partial AUROC stays on the loop
+        return "auroc" if self.max_fpr is None else None
 
     def _metric(self, preds: Tensor, target: Tensor) -> Tensor:
         return retrieval_auroc(preds, target, top_k=self.top_k, max_fpr=self.max_fpr)
@@ -208,10 +227,58 @@ class RetrievalPrecisionRecallCurve(RetrievalMetric):
     def _metric(self, preds: Tensor, target: Tensor) -> Tensor:
         raise NotImplementedError
 
+    def _kernel_curve(self, indexes: Tensor, preds: Tensor, target: Tensor):
+        """The curve from the segmented HIP pass (csrc/retrieval_score.hip): the
+        kernel leaves ``cum_rel[G, max_k]``, the relevant count at every rank, and
+        the divisions and the aggregation over the queries stay in torch as in
+        the functional. None where the kernel does not cover the call."""
+        from metrics_amd.ops import _hip
+        from metrics_amd.retrieval.base import _retrieval_aggregate
+
+        kw = dict(action=self.empty_target_action, aggregation=None, owner=self)
+        res = _hip.retrieval_scores(indexes, preds, target, "curve", phases=1, **kw)
+        if res is None:
+            return None
+        G, longest, shortest = res.header[:3].tolist()  # one transfer
+        max_k = self.max_k or longest
+        # adaptive_k only acts where max_k exceeds a query; that case stays with the functional
+        if G * max_k > _hip.RETRIEVAL_CURVE_MAX_ENTRIES or (self.adaptive_k and max_k > shortest):
+            return None
+        cum_rel = torch.empty((G, max_k), dtype=torch.int32, device=preds.device)
+        res = _hip.retrieval_scores(indexes, preds, target, "curve", phases=2, max_k=max_k, cum_rel=cum_rel, **kw)
+        if res is None:
+            return None
+        empty = res.empty[:G] != 0
+        if self.empty_target_action == "error" and int(res.header[3]):
+            raise ValueError("`compute` method was provided with a query with no positive target.")
+        top_k = torch.arange(1, max_k + 1, device=preds.device)
+        cum = cum_rel.float()
+        precisions = cum / top_k
+        recalls = cum / res.scores[:G].clamp(min=1.0)[:, None]  # scores: the positives of each query
+        if self.empty_target_action == "skip":
+            precisions, recalls = precisions[~empty], recalls[~empty]
+        elif self.empty_target_action in ("neg", "pos"):
+            fill = torch.tensor(1.0 if self.empty_target_action == "pos" else 0.0, device=preds.device)
+            precisions = torch.where(empty[:, None], fill, precisions)
+            recalls = torch.where(empty[:, None], fill, recalls)
+        if not precisions.shape[0]:
+            return torch.zeros(max_k, device=preds.device), torch.zeros(max_k, device=preds.device), top_k
+        return (
+            _retrieval_aggregate(precisions, self.aggregation, dim=0),
+            _retrieval_aggregate(recalls, self.aggregation, dim=0),
+            top_k,
+        )
+
     def compute(self) -> Tuple[Tensor, Tensor, Tensor]:
         indexes = dim_zero_cat(self.indexes)
         preds = dim_zero_cat(self.preds)
         target = dim_zero_cat(self.target)
+
+        if self._kernel_inputs_ok(indexes):
+            # by class: RetrievalRecallAtFixedPrecision borrows this compute()
+            out = RetrievalPrecisionRecallCurve._kernel_curve(self, indexes, preds, target)
+            if out is not None:
+                return out
 
         indexes, indices = torch.sort(indexes)
         preds = preds[indices]
