@@ -22,9 +22,10 @@ ARCH = os.environ.get("METRICS_AMD_ARCH", "gfx950")
 # Sources compiled with flags of their own. lm_nll.hip is built without the
 # packed fp32 instructions (v_pk_add/mul/fma_f32): its folds are scalar per
 # lane, and nothing in it may be paired up by the compiler; retrieval_score.hip
-# likewise keeps its per-lane fp64 sums scalar.
+# likewise keeps its per-lane fp64 sums scalar, and hausdorff.hip the fp32
+# distances of the points a lane holds (rounded one by one like the torch chain).
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-OWN_FLAGS = {"lm_nll.hip": NO_PACKED_FP32, "retrieval_score.hip": NO_PACKED_FP32}
+OWN_FLAGS = {"lm_nll.hip": NO_PACKED_FP32, "retrieval_score.hip": NO_PACKED_FP32, "hausdorff.hip": NO_PACKED_FP32}
 
 
 def build(verbose: bool = True) -> Path:

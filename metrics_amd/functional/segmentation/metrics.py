@@ -202,7 +202,22 @@ def hausdorff_distance(
     if not isinstance(directed, bool):
         raise ValueError(f"Expected argument `directed` must be a boolean, but got {directed}.")
     _check_input_format(input_format)
-    _check_same_shape(preds, target)
+    if input_format == "mixed" and abs(preds.ndim - target.ndim) == 1:
+        # one side holds labels, the other one-hot planes: they agree without the class dimension
+        hot, idx = (preds, target) if preds.ndim > target.ndim else (target, preds)
+        _check_same_shape(hot.select(1, 0) if hot.shape[1] else hot, idx)
+    else:
+        _check_same_shape(preds, target)
+    if preds.is_cuda:
+        # csrc/hausdorff.hip: all planes in one edge pass and one tiled point-set
+        # kernel; None where it does not cover the call (the loop below runs)
+        from metrics_amd.ops import _hip
+
+        out = _hip.hausdorff_distance(
+            preds, target, num_classes, include_background, distance_metric, spacing, directed, input_format
+        )
+        if out is not None:
+            return out
     preds, target = _format_inputs(preds, target, num_classes, input_format)
     if not include_background:
         preds, target = _ignore_background(preds, target)

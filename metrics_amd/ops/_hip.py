@@ -329,6 +329,10 @@ _SIGNATURES = {
     "ma_retrieval_scores": [_U64, _U64, _U64, _U64, _I, _LL, _I, _I, _I, _I, _I, _I, _I, _I, _U64,
                             ctypes.c_ulonglong, _U64, _U64, _U64, _U64],
     "ma_mc_topk_stat": [_U64, _U64, _I, _U64, _LL, _LL, _I, _LL, _I, _U64, _U64, _U64, _U64],
+    "ma_hausdorff_layout": [_LL, _LL, _LL, _LL, ctypes.POINTER(_LL)],
+    "ma_hausdorff_count": [_U64, _U64, _I, _I, _U64, _I, _I, _LL, _LL, _LL, _LL, _U64],
+    "ma_hausdorff_run": [_U64, _U64, _I, _I, _U64, _I, _I, _LL, _LL, _LL, _LL, _U64, _U64, _LL, _LL, _U64, _I, _I,
+                         _F, _F, _U64, _U64],
 }
 
 
@@ -1136,6 +1140,170 @@ def retrieval_records(res: RetrievalScores, G: int) -> dict:
     out["u"] = raw[:, 32:40].contiguous().view(torch.int64)[:, 0]
     out.update({name: dbl[:, i] for i, name in enumerate(("tsum", "ap", "dcg", "idcg"))})
     return out
+
+
+# Hausdorff distance (csrc/hausdorff.hip): every (sample, class) plane of a call
+# in an edge pass and a tiled point-set kernel, one host sync.
+# METRICS_AMD_HAUSDORFF_KERNEL=0 keeps the per-plane torch loop of
+# functional/segmentation/metrics.py everywhere (A/B lever, escape hatch). Read
+# at every call.
+HAUSDORFF_KERNEL_ENV = "METRICS_AMD_HAUSDORFF_KERNEL"
+
+# Points of A a block of the distance kernel holds, words of B in one of its LDS
+# tiles, and the largest H or W of the 16-bit packing (HD_A_TILE, HD_B_TILE,
+# HD_MAX_DIM in csrc/hausdorff.hip; hausdorff_layout holds the two together).
+HAUSDORFF_A_TILE = 1024
+HAUSDORFF_B_TILE = 4096
+HAUSDORFF_MAX_DIM = 32768
+
+_HD_DTYPES = {torch.bool: 0, torch.uint8: 0, torch.int8: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4}
+_HD_METRICS = {"euclidean": 0, "chessboard": 1, "taxicab": 2}
+_HD_LAYOUT_CACHE: dict = {}
+_HD_CALLS = 0
+
+
+def hausdorff_kernel_enabled() -> bool:
+    return os.environ.get(HAUSDORFF_KERNEL_ENV, "1") != "0"
+
+
+def hausdorff_kernel_calls() -> int:
+    """How many calls the Hausdorff kernels have served in this process."""
+    return _HD_CALLS
+
+
+def hausdorff_layout(N: int, C: int, H: int, W: int) -> Optional[tuple]:
+    """(points of A per block, words of B per LDS tile, largest H or W, int32
+    words of the header, edge-pass blocks of an index tensor, of a one-hot
+    tensor) of a call over N samples, C classes and (H, W) planes; None where
+    the kernels do not cover the shape. Host only."""
+    key = (N, C, H, W)
+    if key not in _HD_LAYOUT_CACHE:
+        out = (_LL * 6)()
+        rc = _lib().ma_hausdorff_layout(N, C, H, W, out)
+        if tuple(out[:3]) != (HAUSDORFF_A_TILE, HAUSDORFF_B_TILE, HAUSDORFF_MAX_DIM):
+            raise RuntimeError(
+                f"csrc/hausdorff.hip: tiles and size limit {tuple(out[:3])} differ from the Python constants;"
+                " rebuild the library"
+            )
+        if len(_HD_LAYOUT_CACHE) > 256:
+            _HD_LAYOUT_CACHE.clear()
+        _HD_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _HD_LAYOUT_CACHE[key]
+
+
+def _hd_spacing(spacing) -> Optional[Tuple[float, float, bool]]:
+    """(s0, s1, unit) of a spacing the kernels take, else None."""
+    if spacing is None:
+        return 1.0, 1.0, True
+    if not isinstance(spacing, list) or len(spacing) != 2 or not all(isinstance(s, (int, float)) for s in spacing):
+        return None
+    s0, s1 = (float(torch.tensor(float(s), dtype=torch.float32)) for s in spacing)
+    if not (math.isfinite(s0) and math.isfinite(s1) and s0 >= 0.0 and s1 >= 0.0):
+        return None  # the maximum is kept as the bit pattern of a non-negative float
+    return s0, s1, s0 == 1.0 and s1 == 1.0
+
+
+def _hd_work_table(cnt, c0: int, directed: bool):
+    """From the edge counts ``cnt[tensor, n, c]`` (numpy) and the first listed
+    class: the int64 table of ``ma_hausdorff_run`` (segment starts, half-empty
+    words, work items with the largest first), the number of listed planes, of
+    work items, and of edge words."""
+    import numpy as np
+
+    _, N, C = cnt.shape
+    kept = cnt[:, :, c0:]
+    both = (kept[0] > 0) & (kept[1] > 0)
+    sizes = np.where(both[None], kept, 0)  # a plane with an empty side is inf: its pixels are not written
+    flat = sizes.ravel()
+    offs = (np.cumsum(flat) - flat).reshape(sizes.shape)
+    base = np.full((2, N, C), -1, dtype=np.int64)
+    base[:, :, c0:] = np.where(both[None], offs, -1)
+    K = both.size
+    A = HAUSDORFF_A_TILE
+    items = []
+    for d in (0,) if directed else (0, 1):
+        a_cnt, b_cnt = sizes[d].ravel(), sizes[1 - d].ravel()
+        a_off, b_off = offs[d].ravel(), offs[1 - d].ravel()
+        tiles = -(-a_cnt // A)
+        rep = np.repeat(np.arange(K), tiles)
+        t = np.arange(int(tiles.sum())) - np.repeat(np.cumsum(tiles) - tiles, tiles)
+        items.append(np.stack([a_off[rep] + t * A, np.minimum(A, a_cnt[rep] - t * A), b_off[rep], b_cnt[rep], rep], 1))
+    items = np.concatenate(items)
+    items = items[np.argsort(-(items[:, 1] * items[:, 3]), kind="stable")]
+    table = np.concatenate([base.ravel(), (~both).ravel().astype(np.int64), items.ravel()]).astype(np.int64)
+    return table, K, len(items), int(flat.sum())
+
+
+def hausdorff_distance(
+    preds: Tensor, target: Tensor, num_classes: int, include_background: bool, distance_metric: str,
+    spacing, directed: bool, input_format: str,
+) -> Optional[Tensor]:
+    """The ``(N, C')`` fp32 Hausdorff distances of a call on the current stream:
+    the counting edge pass, ONE readback of the counts and flags (the only host
+    sync), the writing edge pass, ``k_hd_dist`` and the tail. Arguments are
+    those of ``functional.segmentation.hausdorff_distance``, already validated.
+
+    Raises what the torch path raises: ``ValueError`` for a one-hot value that
+    is not 0 / 1, ``RuntimeError`` for a label outside ``[0, num_classes)`` or a
+    listed plane that is empty in both inputs. Returns None without launching
+    anything where the kernels do not cover the call: CPU or float inputs, other
+    than two spatial dimensions, H or W above ``HAUSDORFF_MAX_DIM``, a spacing
+    that is not a list of two non-negative numbers, or the switch off.
+    """
+    global _HD_CALLS
+    sp = _hd_spacing(spacing)
+    if not hausdorff_kernel_enabled() or sp is None or not (preds.is_cuda and target.device == preds.device):
+        return None
+    if preds.dtype not in _HD_DTYPES or target.dtype not in _HD_DTYPES:
+        return None
+    want = {"index": ((3, 3),), "one-hot": ((4, 4),), "mixed": ((3, 4), (4, 3))}[input_format]
+    if (preds.ndim, target.ndim) not in want:
+        return None
+    onehot = [preds.ndim == 4, target.ndim == 4]
+    N, (H, W) = preds.shape[0], preds.shape[-2:]
+    C = num_classes
+    for x, oh in zip((preds, target), onehot):
+        if (x.shape[0], *x.shape[-2:]) != (N, H, W):
+            return None
+        if oh:
+            if input_format == "mixed" and x.shape[1] != num_classes:
+                return None
+            C = x.shape[1]
+    lay = hausdorff_layout(N, C, H, W) if N and C and H and W else None
+    if lay is None:
+        return None
+    lib = _lib()
+    dev = preds.device
+    preds, target = preds.contiguous(), target.contiguous()
+    P = N * C
+    hdr = torch.zeros(lay[3], dtype=torch.int32, device=dev)
+    tensors = (preds.data_ptr(), int(onehot[0]), _HD_DTYPES[preds.dtype],
+               target.data_ptr(), int(onehot[1]), _HD_DTYPES[target.dtype], N, C, H, W, hdr.data_ptr())
+    rc = lib.ma_hausdorff_count(_stream(), *tensors)
+    if rc == -103:
+        return None  # nothing was launched
+    _check(rc, "ma_hausdorff_count")
+    host = hdr[: 1 + 2 * P].cpu().numpy()  # the one host sync of the call
+    if host[0] & 1:
+        raise ValueError("Input x should be binarized")
+    if host[0] & 2:
+        raise RuntimeError(f"Expected every label of an index input to lie in [0, {C}).")
+    c0 = 1 if (not include_background and C > 1) else 0
+    cnt = host[1:].astype("int64").reshape(2, N, C)
+    if ((cnt[0, :, c0:] == 0) & (cnt[1, :, c0:] == 0)).any():
+        raise RuntimeError("Hausdorff distance of a class that is absent from both `preds` and `target`.")
+    table, K, n_items, total = _hd_work_table(cnt, c0, directed)
+    table = torch.from_numpy(table).to(dev)
+    edges = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    cells = torch.zeros(K, dtype=torch.int32, device=dev)
+    out = torch.empty(K, dtype=torch.float32, device=dev)
+    rc = lib.ma_hausdorff_run(
+        _stream(), *tensors, table.data_ptr(), K, n_items, edges.data_ptr(), _HD_METRICS[distance_metric],
+        int(not sp[2]), sp[0], sp[1], cells.data_ptr(), out.data_ptr(),
+    )
+    _check(rc, "ma_hausdorff_run")
+    _HD_CALLS += 1
+    return out.view(N, C - c0)
 
 
 _ERR_OPS = {"sq_err": (0, 1), "abs_err": (1, 1), "ape": (2, 1), "sq_log_err": (3, 1), "moments": (4, 6), "logcosh": (5, 1)}
