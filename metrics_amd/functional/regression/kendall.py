@@ -16,9 +16,11 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from metrics_amd.ops import _hip
 from metrics_amd.utilities.checks import _check_same_shape
 
 _BASE = 64
+_T_VALUE = _hip.KENDALL_RECORD.index("t_value")
 
 
 def _inversions(a: np.ndarray) -> Tuple[int, np.ndarray]:
@@ -100,6 +102,14 @@ def _kendall_corrcoef_compute(
     if preds.ndim == 1:
         preds = preds.unsqueeze(1)
         target = target.unsqueeze(1)
+    # None (and nothing launched): not covered, or an unknown variant; the loop below runs
+    counts = _hip.kendall_counts(preds, target, variant)
+    if counts is not None:
+        tau_t = counts.tau.squeeze()
+        if alternative is None:
+            return tau_t, None  # no host sync
+        # one readback of the record: the t-values, then the p-value exactly as below
+        return tau_t, _p_value(counts.record.cpu().view(torch.float64)[:, _T_VALUE].tolist(), alternative)
     taus = []
     p_values = []
     for d in range(preds.shape[1]):
@@ -135,24 +145,25 @@ def _kendall_corrcoef_compute(
                 t_value = cmd / math.sqrt(denom) if denom == denom and denom > 0 else float("nan")
             p_values.append(t_value)
     tau_t = torch.stack(taus).squeeze()
+    return tau_t, (_p_value(p_values, alternative) if alternative is not None else None)
 
-    p_value = None
-    if alternative is not None:
-        if alternative not in ("two-sided", "greater", "less"):
-            raise ValueError(f"Unknown alternative {alternative}")
-        t = torch.tensor(p_values, dtype=torch.float32)
-        if alternative == "two-sided":
-            t = t.abs()
-        if alternative in ("two-sided", "greater"):
-            t = -t
-        normal = torch.distributions.Normal(0.0, 1.0)
-        is_nan = t.isnan()
-        p_value = normal.cdf(t.nan_to_num())
-        p_value = p_value.where(~is_nan, torch.tensor(float("nan")))
-        if alternative == "two-sided":
-            p_value = 2 * p_value
-        p_value = p_value.squeeze()
-    return tau_t, p_value
+
+def _p_value(t_values, alternative: str) -> Tensor:
+    """The p-value of the per-column t-values (host floats): a CPU fp32 tensor."""
+    if alternative not in ("two-sided", "greater", "less"):
+        raise ValueError(f"Unknown alternative {alternative}")
+    t = torch.tensor(t_values, dtype=torch.float32)
+    if alternative == "two-sided":
+        t = t.abs()
+    if alternative in ("two-sided", "greater"):
+        t = -t
+    normal = torch.distributions.Normal(0.0, 1.0)
+    is_nan = t.isnan()
+    p_value = normal.cdf(t.nan_to_num())
+    p_value = p_value.where(~is_nan, torch.tensor(float("nan")))
+    if alternative == "two-sided":
+        p_value = 2 * p_value
+    return p_value.squeeze()
 
 
 def kendall_rank_corrcoef(

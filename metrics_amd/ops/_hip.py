@@ -333,6 +333,8 @@ _SIGNATURES = {
     "ma_hausdorff_count": [_U64, _U64, _I, _I, _U64, _I, _I, _LL, _LL, _LL, _LL, _U64],
     "ma_hausdorff_run": [_U64, _U64, _I, _I, _U64, _I, _I, _LL, _LL, _LL, _LL, _U64, _U64, _LL, _LL, _U64, _I, _I,
                          _F, _F, _U64, _U64],
+    "ma_kendall_layout": [_LL, _LL, ctypes.POINTER(_LL)],
+    "ma_kendall": [_U64, _U64, _U64, _I, _LL, _LL, _I, _U64, ctypes.c_ulonglong, _U64, _U64],
 }
 
 
@@ -1304,6 +1306,125 @@ def hausdorff_distance(
     _check(rc, "ma_hausdorff_run")
     _HD_CALLS += 1
     return out.view(N, C - c0)
+
+
+# Kendall rank correlation (csrc/kendall.hip): the pair counts of every column
+# of a call by a counting merge sort, no host sync.
+# METRICS_AMD_KENDALL_KERNEL=0 keeps the numpy path of
+# functional/regression/kendall.py everywhere (A/B lever, escape hatch). Read at
+# every call.
+KENDALL_KERNEL_ENV = "METRICS_AMD_KENDALL_KERNEL"
+
+# y-keys a block sorts in LDS, the largest n covered (about 24 bytes of scratch
+# per element: 6 GiB there), words of the sibling run a merge block stages in
+# LDS and keys of a merge chunk (KD_TILE, KD_MAX_N, KD_STAGE, KD_CHUNK in
+# csrc/kendall.hip; kendall_layout holds the two together).
+KENDALL_TILE = 4096
+KENDALL_MAX_N = 2**28
+KENDALL_STAGE = 4096
+KENDALL_CHUNK = 1024
+
+# the 8-byte words of a column's record, in order
+KENDALL_RECORD = ("con", "dis", "x_ties", "y_ties", "xy_ties", "unique_x", "unique_y",  # int64
+                  "p1_x", "p2_x", "p1_y", "p2_y", "tau", "t_value",                      # fp64
+                  "lds_chunks", "global_chunks", "nan")                                  # int64
+_KD_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_KD_VARIANTS = {"a": 0, "b": 1, "c": 2}
+_KD_LAYOUT_CACHE: dict = {}
+_KD_FUNCTIONAL_OWNERS: dict = {}
+_KD_CALLS = 0
+
+
+class _KendallOwner:
+    """Holds the scratch of calls without an owner, one per device."""
+
+
+class KendallCounts(NamedTuple):
+    """What one call left on the device: ``record`` is (D, 16) int64, a row per
+    column with the words of ``KENDALL_RECORD`` (view the row as float64 for the
+    fp64 words), ``tau`` the (D,) fp32 coefficients."""
+
+    record: Tensor
+    tau: Tensor
+
+    def fields(self) -> dict:
+        """The record by field name, as (D,) tensors (copies)."""
+        dbl = self.record.view(torch.float64)
+        return {name: (dbl if 7 <= i <= 12 else self.record)[:, i].clone() for i, name in enumerate(KENDALL_RECORD)}
+
+
+def kendall_kernel_enabled() -> bool:
+    return os.environ.get(KENDALL_KERNEL_ENV, "1") != "0"
+
+
+def kendall_kernel_calls() -> int:
+    """How many calls the Kendall kernels have served in this process."""
+    return _KD_CALLS
+
+
+def kendall_layout(n: int, D: int = 1) -> Optional[tuple]:
+    """(keys per LDS tile, largest n, words of the LDS stage, keys per merge
+    chunk, words of a record, scratch bytes, tile blocks, global merge levels)
+    of a call over ``n`` rows and ``D`` columns; None where it is not covered.
+    Host only."""
+    key = (n, D)
+    if key not in _KD_LAYOUT_CACHE:
+        out = (_LL * 8)()
+        rc = _lib().ma_kendall_layout(n, D, out)
+        if tuple(out[:5]) != (KENDALL_TILE, KENDALL_MAX_N, KENDALL_STAGE, KENDALL_CHUNK, len(KENDALL_RECORD)):
+            raise RuntimeError(
+                f"csrc/kendall.hip: tile, size limit, stage, chunk and record {tuple(out[:5])} differ from the"
+                " Python constants; rebuild the library"
+            )
+        if rc not in (0, -103):
+            _check(rc, "ma_kendall_layout")
+        if len(_KD_LAYOUT_CACHE) > 256:
+            _KD_LAYOUT_CACHE.clear()
+        _KD_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _KD_LAYOUT_CACHE[key]
+
+
+def kendall_counts(preds: Tensor, target: Tensor, variant: str, owner=None) -> Optional[KendallCounts]:
+    """The Kendall record and fp32 tau of every column of ``(n,)`` or ``(n, D)``
+    inputs in ONE native call on the current stream: keys, sort, run statistics,
+    LDS tile sort with inversion count, global rank-merge levels, tail. The
+    scratch lives in the ``__dict__`` of ``owner``. No host sync.
+
+    Returns None without launching anything where the kernels do not cover the
+    call: CPU tensors, fp64 or integer inputs, more than two dimensions,
+    ``n < 2``, ``n > KENDALL_MAX_N``, or the switch off.
+    """
+    global _KD_CALLS
+    if not kendall_kernel_enabled() or not (preds.is_cuda and target.device == preds.device):
+        return None
+    if preds.dtype not in _KD_DTYPES or target.dtype not in _KD_DTYPES or variant not in _KD_VARIANTS:
+        return None
+    if preds.ndim not in (1, 2) or preds.shape != target.shape:
+        return None
+    n, D = preds.shape[0], (preds.shape[1] if preds.ndim == 2 else 1)
+    lay = kendall_layout(n, D) if 2 <= n <= KENDALL_MAX_N and D >= 1 else None
+    if lay is None:
+        return None
+    if preds.dtype != target.dtype:
+        preds, target = preds.float(), target.float()  # exact
+    preds, target = preds.contiguous(), target.contiguous()
+    dev = preds.device
+    if owner is None:
+        owner = _KD_FUNCTIONAL_OWNERS.get(dev)
+        if owner is None:
+            owner = _KD_FUNCTIONAL_OWNERS[dev] = _KendallOwner()
+    scratch = owner_buffer(owner, "_hip_kendall_scratch", (lay[5],), torch.uint8, dev, zero=False, grow=True)
+    record = torch.empty((D, len(KENDALL_RECORD)), dtype=torch.int64, device=dev)
+    tau = torch.empty(D, dtype=torch.float32, device=dev)
+    rc = _lib().ma_kendall(
+        _stream(), preds.data_ptr(), target.data_ptr(), _KD_DTYPES[preds.dtype], n, D, _KD_VARIANTS[variant],
+        scratch.data_ptr(), scratch.numel(), record.data_ptr(), tau.data_ptr(),
+    )
+    if rc == -103:
+        return None  # nothing was launched
+    _check(rc, "ma_kendall")
+    _KD_CALLS += 1
+    return KendallCounts(record, tau)
 
 
 _ERR_OPS = {"sq_err": (0, 1), "abs_err": (1, 1), "ape": (2, 1), "sq_log_err": (3, 1), "moments": (4, 6), "logcosh": (5, 1)}
