@@ -3,8 +3,8 @@
 // Implements the reference's `_binary_clf_curve`
 // (torchmetrics functional/classification/precision_recall_curve.py:30-82):
 // descending sort of the scores, cumulative tp/fp at each DISTINCT score.
-// MI355X-native formulation: rocPRIM device radix sort (stable, fp32 keys)
-// + double-precision device scans + a fused gather/flag kernel and a fused
+// MI355X-native formulation: rocPRIM device radix sort (stable, canonical
+// 32-bit keys of the fp32 scores: desc_key below) + double-precision device scans + a fused gather/flag kernel and a fused
 // compaction kernel, all launched on the caller's torch HIP stream.
 // Counts are integers (< 2^53), so the fp64 scan is bit-exact for the
 // unweighted path and at least as accurate as the reference's fp32 cumsum
@@ -37,15 +37,35 @@ static inline size_t align_up(size_t x) { return (x + ALIGN - 1) & ~(ALIGN - 1);
 
 // ---------------------------------------------------------------- kernels
 
-__global__ void __launch_bounds__(256) k_iota(int* idx, ll n) {
+// Sort key of a score: the larger the score, the smaller the key, and two
+// scores share a key exactly where float == holds. -0.0 takes the key of +0.0.
+// Every NaN, whatever its sign and payload, takes NAN_KEY, in front of +inf,
+// where torch.argsort(descending=True) puts it; no other value maps there
+// (key 0 would be the bit pattern 0x7FFFFFFF, itself a NaN). A NaN equals
+// nothing, so the flag kernels end a tie group at every NAN_KEY.
+static constexpr unsigned int NAN_KEY = 0u;
+
+__device__ __forceinline__ unsigned int desc_key(float v) {
+    unsigned int b = __float_as_uint(v);
+    if ((b & 0x7FFFFFFFu) > 0x7F800000u) return NAN_KEY;
+    if (b == 0x80000000u) b = 0u;
+    // ascending-order-preserving flip, then invert for descending score
+    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ~b;
+}
+
+__global__ void __launch_bounds__(256) k_keys(
+    const float* __restrict__ preds, ll n, unsigned int* __restrict__ keys, int* __restrict__ idx) {
     ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) idx[i] = (int)i;
+    if (i >= n) return;
+    keys[i] = desc_key(preds[i]);
+    idx[i] = (int)i;
 }
 
 // Gather target/weight through the sort permutation and mark distinct-score
 // boundaries in one pass.
 __global__ void __launch_bounds__(256) k_gather_flags(
-    const float* __restrict__ keys_sorted, const int* __restrict__ idx_sorted,
+    const unsigned int* __restrict__ keys_sorted, const int* __restrict__ idx_sorted,
     const ll* __restrict__ target, const float* __restrict__ weight, ll n,
     ll pos_label, double* __restrict__ tvals, double* __restrict__ fvals,
     int* __restrict__ flags) {
@@ -56,13 +76,16 @@ __global__ void __launch_bounds__(256) k_gather_flags(
     const double w = weight ? (double)weight[src] : 1.0;
     tvals[i] = t * w;
     if (fvals) fvals[i] = (1.0 - t) * w;
-    flags[i] = (i == n - 1) || (keys_sorted[i] != keys_sorted[i + 1]);
+    const unsigned int k = keys_sorted[i];
+    flags[i] = (i == n - 1) || (k == NAN_KEY) || (k != keys_sorted[i + 1]);
 }
 
 // Compact (tps, fps, thresholds) at the flagged positions. pos_scan is the
-// INCLUSIVE scan of flags, so out position = pos_scan[i] - 1.
+// INCLUSIVE scan of flags, so out position = pos_scan[i] - 1. The threshold
+// is the score itself (of the last element of the tie group), not its key.
 __global__ void __launch_bounds__(256) k_compact(
-    const float* __restrict__ keys_sorted, const int* __restrict__ flags,
+    const float* __restrict__ preds, const int* __restrict__ idx_sorted,
+    const int* __restrict__ flags,
     const int* __restrict__ pos_scan, const double* __restrict__ tps_full,
     const double* __restrict__ fps_full /* null => unweighted */, ll n,
     float* __restrict__ out_fps, float* __restrict__ out_tps,
@@ -74,7 +97,7 @@ __global__ void __launch_bounds__(256) k_compact(
         const double tp = tps_full[i];
         out_tps[o] = (float)tp;
         out_fps[o] = fps_full ? (float)fps_full[i] : (float)((double)(i + 1) - tp);
-        out_thresh[o] = keys_sorted[i];
+        out_thresh[o] = preds[idx_sorted[i]];
     }
     if (i == n - 1) *out_count = (ll)pos_scan[n - 1];
 }
@@ -84,9 +107,9 @@ __global__ void __launch_bounds__(256) k_compact(
 extern "C" int ma_clf_curve_scratch_bytes(ll n, int weighted, unsigned long long* out_bytes) {
     size_t sort_tmp = 0, scan_tmp = 0, iscan_tmp = 0;
     hipError_t e;
-    e = rocprim::radix_sort_pairs_desc((void*)nullptr, sort_tmp, (const float*)nullptr,
-                                       (float*)nullptr, (const int*)nullptr, (int*)nullptr,
-                                       (size_t)n);
+    e = rocprim::radix_sort_pairs((void*)nullptr, sort_tmp, (const unsigned int*)nullptr,
+                                  (unsigned int*)nullptr, (const int*)nullptr, (int*)nullptr,
+                                  (size_t)n);
     if (e != hipSuccess) return (int)e;
     e = rocprim::inclusive_scan((void*)nullptr, scan_tmp, (const double*)nullptr,
                                 (double*)nullptr, (size_t)n, rocprim::plus<double>());
@@ -99,7 +122,8 @@ extern "C" int ma_clf_curve_scratch_bytes(ll n, int weighted, unsigned long long
     if (iscan_tmp > tmp) tmp = iscan_tmp;
 
     size_t total = 0;
-    total += align_up((size_t)n * sizeof(float));   // keys_sorted
+    total += align_up((size_t)n * sizeof(unsigned int));  // keys
+    total += align_up((size_t)n * sizeof(unsigned int));  // keys_sorted
     total += align_up((size_t)n * sizeof(int));     // idx (iota)
     total += align_up((size_t)n * sizeof(int));     // idx_sorted
     total += align_up((size_t)n * sizeof(double));  // tvals / tps_full (in-place scan)
@@ -121,7 +145,8 @@ extern "C" int ma_binary_clf_curve(
     const float* weight = (const float*)weight_u;  // may be null
 
     char* p = (char*)scratch_u;
-    float* keys_sorted = (float*)p;          p += align_up((size_t)n * sizeof(float));
+    unsigned int* keys = (unsigned int*)p;   p += align_up((size_t)n * sizeof(unsigned int));
+    unsigned int* keys_sorted = (unsigned int*)p; p += align_up((size_t)n * sizeof(unsigned int));
     int* idx = (int*)p;                      p += align_up((size_t)n * sizeof(int));
     int* idx_sorted = (int*)p;               p += align_up((size_t)n * sizeof(int));
     double* tvals = (double*)p;              p += align_up((size_t)n * sizeof(double));
@@ -135,10 +160,10 @@ extern "C" int ma_binary_clf_curve(
     const int B = 256;
     const ll grid = (n + B - 1) / B;
 
-    hipLaunchKernelGGL(k_iota, dim3(grid), dim3(B), 0, stream, idx, n);
+    hipLaunchKernelGGL(k_keys, dim3(grid), dim3(B), 0, stream, preds, n, keys, idx);
     size_t tmp_bytes = rp_bytes;
-    OK(rocprim::radix_sort_pairs_desc(rp_tmp, tmp_bytes, preds, keys_sorted, idx, idx_sorted,
-                                      (size_t)n, 0, 32, stream));
+    OK(rocprim::radix_sort_pairs(rp_tmp, tmp_bytes, keys, keys_sorted, idx, idx_sorted,
+                                 (size_t)n, 0, 32, stream));
     hipLaunchKernelGGL(k_gather_flags, dim3(grid), dim3(B), 0, stream, keys_sorted, idx_sorted,
                        target, weight, n, pos_label, tvals, fvals, flags);
     tmp_bytes = rp_bytes;
@@ -152,8 +177,8 @@ extern "C" int ma_binary_clf_curve(
     tmp_bytes = rp_bytes;
     OK(rocprim::inclusive_scan(rp_tmp, tmp_bytes, flags, pos_scan, (size_t)n,
                                rocprim::plus<int>(), stream));
-    hipLaunchKernelGGL(k_compact, dim3(grid), dim3(B), 0, stream, keys_sorted, flags, pos_scan,
-                       tvals, fvals, n, (float*)out_fps_u, (float*)out_tps_u,
+    hipLaunchKernelGGL(k_compact, dim3(grid), dim3(B), 0, stream, preds, idx_sorted, flags,
+                       pos_scan, tvals, fvals, n, (float*)out_fps_u, (float*)out_tps_u,
                        (float*)out_thresh_u, (ll*)out_count_u);
     return (int)hipGetLastError();
 }
@@ -169,10 +194,9 @@ __global__ void __launch_bounds__(256) k_retrieval_keys(
     unsigned long long* __restrict__ keys, unsigned int* __restrict__ ikeys, int* __restrict__ pos) {
     ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    unsigned int b = __float_as_uint(preds[i]);
-    // ascending-order-preserving flip, then invert for descending score
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    b = ~b;
+    // +0.0 and -0.0 share a key and every NaN leads its query, as in the stable
+    // torch lexsort; the caller keeps indexes outside [0, 2^31) off this kernel
+    const unsigned int b = desc_key(preds[i]);
     keys[i] = ((unsigned long long)(unsigned int)idx[i] << 32) | (unsigned long long)b;
     ikeys[i] = (unsigned int)idx[i];
     pos[i] = (int)i;
@@ -239,9 +263,7 @@ __global__ void __launch_bounds__(256) k_mc_keys(
     ll e = (ll)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= B * C) return;
     const ll c = e % C;  // element e = (row, c) row-major
-    unsigned int b = __float_as_uint(probs[e]);
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    b = ~b;  // descending within class
+    const unsigned int b = desc_key(probs[e]);  // descending within class
     keys[e] = ((unsigned long long)c << 32) | (unsigned long long)b;
     pos[e] = (int)e;
 }
@@ -256,7 +278,8 @@ __global__ void __launch_bounds__(256) k_mc_gather_flags(
     const ll row = src / C;
     const ll cls = (ll)(keys_sorted[i] >> 32);
     tvals[i] = (target[row] == cls) ? 1.0 : 0.0;
-    flags[i] = (i == n - 1) || (keys_sorted[i] != keys_sorted[i + 1]);
+    const unsigned long long k = keys_sorted[i];
+    flags[i] = (i == n - 1) || ((unsigned int)k == NAN_KEY) || (k != keys_sorted[i + 1]);
 }
 
 // multilabel variant: target is (B, C) 0/1
@@ -267,7 +290,8 @@ __global__ void __launch_bounds__(256) k_ml_gather_flags(
     ll i = (ll)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     tvals[i] = (double)target[pos_sorted[i]];
-    flags[i] = (i == n - 1) || (keys_sorted[i] != keys_sorted[i + 1]);
+    const unsigned long long k = keys_sorted[i];
+    flags[i] = (i == n - 1) || ((unsigned int)k == NAN_KEY) || (k != keys_sorted[i + 1]);
 }
 
 __global__ void __launch_bounds__(256) k_mc_compact(

@@ -41,10 +41,12 @@ def _binary_clf_curve(
 
         if preds.is_cuda and preds.numel() > 0:
             # K2 HIP path: rocPRIM radix sort + fused fp64 scans (csrc/clf_curve.hip)
-            fps, tps, thr = ops.hip_binary_clf_curve(
+            # (fp64 scores and sizes beyond its 32-bit positions take the torch path below)
+            res = ops.hip_binary_clf_curve(
                 preds, target, sample_weights if isinstance(sample_weights, Tensor) else None, pos_label
             )
-            return fps, tps, thr.to(preds.dtype)
+            if res is not None:
+                return res[0], res[1], res[2].to(preds.dtype)
 
         desc_score_indices = torch.argsort(preds, descending=True)
 

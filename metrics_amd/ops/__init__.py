@@ -26,8 +26,13 @@ def hip_bincount(x: Tensor, minlength: int) -> Tensor:
 
 
 def hip_mc_clf_curve(probs: Tensor, target: Tensor, multilabel: bool = False):
-    """Batched per-class exact curves (one composite-key sort) — GPU only."""
+    """Batched per-class exact curves (one composite-key sort) — GPU only.
+
+    A list of None, one per class, where the kernel does not cover the call
+    (``_hip.mc_clf_curve``): each class then goes through ``_binary_clf_curve``."""
     out = _hip.mc_clf_curve(probs, target, multilabel)
+    if out is None:
+        return [None] * probs.shape[1]
     if probs.dtype != torch.float32:
         out = [(f, t, thr.to(probs.dtype), p, n) for f, t, thr, p, n in out]
     return out
@@ -36,7 +41,8 @@ def hip_mc_clf_curve(probs: Tensor, target: Tensor, multilabel: bool = False):
 def hip_binary_clf_curve(
     preds: Tensor, target: Tensor, weights: Optional[Tensor] = None, pos_label: int = 1
 ) -> Tuple[Tensor, Tensor, Tensor]:
-    """Exact clf-curve core (fps, tps, thresholds) — GPU only (K2 kernel)."""
+    """Exact clf-curve core (fps, tps, thresholds) — GPU only (K2 kernel). None
+    where the kernel does not cover the call (``_hip.binary_clf_curve``)."""
     return _hip.binary_clf_curve(preds, target, weights, pos_label)
 
 

@@ -841,17 +841,42 @@ def multiclass_curve_confmat(
 
 _CLF_SCRATCH_CACHE: dict = {}
 
+# Exact-curve and retrieval-sort kernels (csrc/clf_curve.hip): positions and
+# output offsets are 32-bit, so a call over more elements than this is kept off
+# them. fp64 scores are kept off too: the sort keys are fp32, and two fp64
+# scores closer than an fp32 ulp would share a threshold. The torch path of the
+# caller serves both.
+EXACT_CURVE_MAX_ELEMENTS = 2**31 - 1
+_EC_CALLS = {"kernel": 0, "kept_off": 0}
+
+
+def exact_curve_calls() -> dict:
+    """How many calls ``binary_clf_curve`` / ``mc_clf_curve`` / ``retrieval_sort``
+    have served (``kernel``) and returned None for (``kept_off``) in this process."""
+    return dict(_EC_CALLS)
+
+
+def _exact_curve_covers(scores: Tensor) -> bool:
+    ok = scores.dtype != torch.float64 and 0 < scores.numel() <= EXACT_CURVE_MAX_ELEMENTS
+    _EC_CALLS["kernel" if ok else "kept_off"] += 1
+    return ok
+
 
 def binary_clf_curve(
     preds: Tensor, target: Tensor, weights: Optional[Tensor] = None, pos_label: int = 1
-) -> Tuple[Tensor, Tensor, Tensor]:
+) -> Optional[Tuple[Tensor, Tensor, Tensor]]:
     """Exact (fps, tps, thresholds) at distinct descending scores.
 
-    rocPRIM radix sort (stable, fp32 keys) + fp64 device scans + fused
-    gather/flag and compaction kernels — the K2 path for thresholds=None
-    ROC/PR/AUROC. One D2H sync for the data-dependent output length (the
-    reference's torch path syncs there too).
+    rocPRIM radix sort (stable, canonical 32-bit keys of the fp32 scores) +
+    fp64 device scans + fused gather/flag and compaction kernels — the K2 path
+    for thresholds=None ROC/PR/AUROC. One D2H sync for the data-dependent
+    output length (the reference's torch path syncs there too). ``fps`` and
+    ``tps`` are fp32: the exact fp64 scan result rounded to nearest once.
+    None, with nothing launched, for fp64 scores, no element or more than
+    ``EXACT_CURVE_MAX_ELEMENTS`` of them.
     """
+    if not _exact_curve_covers(preds):
+        return None
     lib = _lib()
     preds = _to_supported(preds)
     if preds.dtype != torch.float32:
@@ -902,9 +927,12 @@ def mc_clf_curve(probs: Tensor, target: Tensor, multilabel: bool = False):
     """Per-class exact curves for ALL classes in one composite-key sort.
 
     ``probs`` (B, C); ``target`` (B,) class ids (multiclass) or (B, C) 0/1
-    (multilabel). Returns a list of C ``(fps, tps, thresholds)`` tuples —
-    one device sort + ONE host count transfer instead of C sorts + C syncs.
+    (multilabel). Returns a list of C ``(fps, tps, thresholds, n_pos, n_neg)``
+    tuples — one device sort + ONE host count transfer instead of C sorts + C
+    syncs. None where ``binary_clf_curve`` returns None.
     """
+    if not _exact_curve_covers(probs):
+        return None
     lib = _lib()
     probs = _to_supported(probs)
     if probs.dtype != torch.float32:
@@ -949,7 +977,9 @@ def mc_clf_curve(probs: Tensor, target: Tensor, multilabel: bool = False):
     if multilabel:
         pos = target.sum(0)
     else:
-        pos = torch.bincount(target.clamp(min=0), minlength=C)[:C]
+        # a target outside [0, C) (-1 for a row kept as a negative of every
+        # class) is no class's positive: bin 0 of the shifted count drops it
+        pos = torch.bincount((target + 1).clamp(min=0), minlength=C + 1)[1 : C + 1]
     packed = torch.cat([out_counts, pos]).cpu()
     counts = packed[:C].tolist()
     pos_counts = packed[C:].tolist()
@@ -968,13 +998,16 @@ def mc_clf_curve(probs: Tensor, target: Tensor, multilabel: bool = False):
 _RETR_SCRATCH_CACHE: dict = {}
 
 
-def retrieval_sort(indexes: Tensor, preds: Tensor) -> Tuple[Tensor, Tensor]:
+def retrieval_sort(indexes: Tensor, preds: Tensor) -> Optional[Tuple[Tensor, Tensor]]:
     """(order, by_index) permutations for retrieval grouping in ONE radix pass.
 
     ``order`` sorts by (query index asc, pred desc); ``by_index`` by index
     only with original order preserved for ties. Composite 64-bit keys
-    replace the torch double-argsort lexsort. Requires indexes < 2^31.
+    replace the torch double-argsort lexsort. Requires indexes in [0, 2^31):
+    the caller checks that. None where ``binary_clf_curve`` returns None.
     """
+    if not _exact_curve_covers(preds):
+        return None
     lib = _lib()
     indexes = indexes.contiguous().long()
     preds = _to_supported(preds).float().contiguous()

@@ -57,13 +57,20 @@ class _Grouped:
 
 def _group_by_query(indexes: Tensor, preds: Tensor, target: Tensor) -> _Grouped:
     g = _Grouped()
-    if indexes.is_cuda and indexes.numel() and int(indexes.max()) < 2**31:
-        # ONE composite-key rocPRIM radix pass for the whole lexsort
-        # (csrc/clf_curve.hip ma_retrieval_sort); one more 32-bit sort gives
-        # the stable by-index order
-        from metrics_amd.ops import _hip
+    sorted_pair = None
+    if indexes.is_cuda and indexes.numel():
+        # the kernel's keys hold the index as 32 unsigned bits: a negative index
+        # would sort behind every other, so it takes the torch path like one >= 2^31
+        lo, hi = torch.stack(torch.aminmax(indexes)).tolist()
+        if lo >= 0 and hi < 2**31:
+            # ONE composite-key rocPRIM radix pass for the whole lexsort
+            # (csrc/clf_curve.hip ma_retrieval_sort); one more 32-bit sort gives
+            # the stable by-index order. None: fp64 scores or too many elements
+            from metrics_amd.ops import _hip
 
-        order, by_index = _hip.retrieval_sort(indexes, preds)
+            sorted_pair = _hip.retrieval_sort(indexes, preds)
+    if sorted_pair is not None:
+        order, by_index = sorted_pair
     else:
         # lexsort: stable pred-desc, then stable index-asc => index asc, pred desc
         order1 = torch.argsort(preds, descending=True, stable=True)
