@@ -6,6 +6,7 @@ from typing import Tuple
 import torch
 from torch import Tensor
 
+from metrics_amd.ops import _hip
 from metrics_amd.utilities.checks import _check_same_shape
 
 
@@ -51,7 +52,12 @@ def _spearman_corrcoef_update(preds: Tensor, target: Tensor, num_outputs: int) -
     return preds, target
 
 
-def _spearman_corrcoef_compute(preds: Tensor, target: Tensor, eps: float = 1e-6) -> Tensor:
+def _spearman_corrcoef_compute(preds: Tensor, target: Tensor, eps: float = 1e-6, owner=None) -> Tensor:
+    # CUDA fp32 / bf16 / fp16: csrc/spearman.hip, exact rank sums and no host sync (the kernel's eps is 1e-6)
+    res = _hip.spearman_ranks(preds, target, owner) if eps == 1e-6 else None
+    if res is not None:
+        rho = res.rho.to(torch.promote_types(preds.dtype, target.dtype))
+        return rho.squeeze(0) if preds.ndim == 1 else rho
     if preds.ndim == 1:
         preds = _rank_data(preds)
         target = _rank_data(target)

@@ -335,6 +335,8 @@ _SIGNATURES = {
                          _F, _F, _U64, _U64],
     "ma_kendall_layout": [_LL, _LL, ctypes.POINTER(_LL)],
     "ma_kendall": [_U64, _U64, _U64, _I, _LL, _LL, _I, _U64, ctypes.c_ulonglong, _U64, _U64],
+    "ma_spearman_layout": [_LL, _LL, ctypes.POINTER(_LL)],
+    "ma_spearman": [_U64, _U64, _U64, _I, _LL, _LL, _U64, ctypes.c_ulonglong, _U64, _U64],
 }
 
 
@@ -1458,6 +1460,130 @@ def kendall_counts(preds: Tensor, target: Tensor, variant: str, owner=None) -> O
     _check(rc, "ma_kendall")
     _KD_CALLS += 1
     return KendallCounts(record, tau)
+
+
+# Spearman rank correlation (csrc/spearman.hip): two radix sorts and two rank
+# passes over all columns of a call at once, exact integer rank sums, no host
+# sync. METRICS_AMD_SPEARMAN_KERNEL=0 keeps the torch chain of
+# functional/regression/spearman.py everywhere (A/B lever, escape hatch). Read
+# at every call.
+SPEARMAN_KERNEL_ENV = "METRICS_AMD_SPEARMAN_KERNEL"
+
+# sorted keys a rank block stages in LDS (below it columns are packed into a
+# block), the largest n * D covered (about 24 bytes of scratch per element:
+# 6 GiB there) and the largest D (SP_TILE, SP_MAX_ELEMS, SP_MAX_D in
+# csrc/spearman.hip; spearman_layout holds the two together).
+SPEARMAN_TILE = 2048
+SPEARMAN_MAX_ELEMS = 2**28
+SPEARMAN_MAX_D = 65536
+
+# the 8-byte words of a column's record, in order: the three sums over
+# a = 2 rank_x - (n + 1) and b = 2 rank_y - (n + 1) as 128-bit integers
+# (lo unsigned, hi signed), the run counts, rho as fp64, the NaN-seen flag
+SPEARMAN_RECORD = ("sab_lo", "sab_hi", "saa_lo", "saa_hi", "sbb_lo", "sbb_hi", "runs_x", "runs_y", "rho", "nan")
+_SP_LAYOUT_CACHE: dict = {}
+_SP_FUNCTIONAL_OWNERS: dict = {}
+_SP_CALLS = 0
+
+
+class _SpearmanOwner:
+    """Holds the scratch of calls without an owner, one per device."""
+
+
+class SpearmanResult(NamedTuple):
+    """What one call left on the device: ``record`` is (D, 10) int64, a row per
+    column with the words of ``SPEARMAN_RECORD`` (view the row as float64 for
+    ``rho``), ``rho`` the (D,) fp32 coefficients."""
+
+    record: Tensor
+    rho: Tensor
+
+    def sums(self) -> list:
+        """Per column ``{"sab", "saa", "sbb"}`` as exact Python ints plus the
+        run counts and the NaN flag. Reads the record back (a host sync)."""
+        out = []
+        for row in self.record.tolist():
+            f = dict(zip(SPEARMAN_RECORD, row))
+            col = {k: f[k + "_hi"] * 2**64 + f[k + "_lo"] % 2**64 for k in ("sab", "saa", "sbb")}
+            col.update(runs_x=f["runs_x"], runs_y=f["runs_y"], nan=f["nan"])
+            out.append(col)
+        return out
+
+
+def spearman_kernel_enabled() -> bool:
+    return os.environ.get(SPEARMAN_KERNEL_ENV, "1") != "0"
+
+
+def spearman_kernel_calls() -> int:
+    """How many calls the Spearman kernels have served in this process."""
+    return _SP_CALLS
+
+
+def spearman_layout(n: int, D: int = 1) -> Optional[tuple]:
+    """(keys per LDS tile, largest n * D, largest D, words of a record, scratch
+    bytes, 1 for the packed mapping, blocks of a rank pass, slots per column) of
+    a call over ``n`` rows and ``D`` columns; None where it is not covered.
+    Host only."""
+    key = (n, D)
+    if key not in _SP_LAYOUT_CACHE:
+        out = (_LL * 8)()
+        rc = _lib().ma_spearman_layout(n, D, out)
+        if tuple(out[:4]) != (SPEARMAN_TILE, SPEARMAN_MAX_ELEMS, SPEARMAN_MAX_D, len(SPEARMAN_RECORD)):
+            raise RuntimeError(
+                f"csrc/spearman.hip: tile, element limit, column limit and record {tuple(out[:4])} differ from the"
+                " Python constants; rebuild the library"
+            )
+        if rc not in (0, -103):
+            _check(rc, "ma_spearman_layout")
+        if len(_SP_LAYOUT_CACHE) > 256:
+            _SP_LAYOUT_CACHE.clear()
+        _SP_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _SP_LAYOUT_CACHE[key]
+
+
+def spearman_ranks(preds: Tensor, target: Tensor, owner=None) -> Optional[SpearmanResult]:
+    """The Spearman record and fp32 rho of every column of ``(n,)`` or ``(n, D)``
+    inputs in ONE native call on the current stream: keys, sort by x, rank pass,
+    sort by y, rank pass with the three exact sums, tail. The scratch lives in
+    the ``__dict__`` of ``owner``. No host sync.
+
+    Returns None without launching anything where the kernels do not cover the
+    call: CPU tensors, fp64 or integer inputs, more than two dimensions, a shape
+    mismatch, ``n < 2``, ``n * D > SPEARMAN_MAX_ELEMS``, ``D > SPEARMAN_MAX_D``,
+    or the switch off.
+    """
+    global _SP_CALLS
+    if not spearman_kernel_enabled() or not (preds.is_cuda and target.device == preds.device):
+        return None
+    if preds.dtype not in _KD_DTYPES or target.dtype not in _KD_DTYPES:
+        return None
+    if preds.ndim not in (1, 2) or preds.shape != target.shape:
+        return None
+    n, D = preds.shape[0], (preds.shape[1] if preds.ndim == 2 else 1)
+    covered = n >= 2 and 1 <= D <= SPEARMAN_MAX_D and n * D <= SPEARMAN_MAX_ELEMS
+    lay = spearman_layout(n, D) if covered else None
+    if lay is None:
+        return None
+    if preds.dtype != target.dtype:
+        preds, target = preds.float(), target.float()  # exact
+    preds, target = preds.contiguous(), target.contiguous()
+    dev = preds.device
+    if owner is None:
+        owner = _SP_FUNCTIONAL_OWNERS.get(dev)
+        if owner is None:
+            owner = _SP_FUNCTIONAL_OWNERS[dev] = _SpearmanOwner()
+    scratch = owner_buffer(owner, "_hip_spearman_scratch", (lay[4],), torch.uint8, dev, zero=False, grow=True)
+    record = torch.empty((D, len(SPEARMAN_RECORD)), dtype=torch.int64, device=dev)
+    rho = torch.empty(D, dtype=torch.float32, device=dev)
+    rc = _lib().ma_spearman(
+        _stream(), preds.data_ptr(), target.data_ptr(), _KD_DTYPES[preds.dtype], n, D,
+        scratch.data_ptr(), scratch.numel(), record.data_ptr(), rho.data_ptr(),
+    )
+    if rc == -103:
+        return None  # nothing was launched
+    _check(rc, "ma_spearman")
+    _SP_CALLS += 1
+    return SpearmanResult(record, rho)
 
 
 _ERR_OPS = {"sq_err": (0, 1), "abs_err": (1, 1), "ape": (2, 1), "sq_log_err": (3, 1), "moments": (4, 6), "logcosh": (5, 1)}

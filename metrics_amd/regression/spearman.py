@@ -41,7 +41,7 @@ class SpearmanCorrCoef(Metric):
         """Spearman correlation over all accumulated data."""
         preds = dim_zero_cat(self.preds)
         target = dim_zero_cat(self.target)
-        return _spearman_corrcoef_compute(preds, target)
+        return _spearman_corrcoef_compute(preds, target, owner=self)
 
     def plot(self, val: Optional[Any] = None, ax: Optional[Any] = None):
         return self._plot(val, ax)
