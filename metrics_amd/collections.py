@@ -593,10 +593,13 @@ class _FusedMulticlassComputePlan:
     """Collection-level compute: every member that declares what it computes
     (``Metric._compute_plan_spec``) over the stat-scores, confusion-matrix,
     exact-match or threshold-curve group gets its result from ONE native call
-    of at most three launches (``csrc/mc_compute.hip``) instead of one Python
-    wrapper, cache lookup, allocation and launch per metric. The step also
-    performs the curve leader's lazy flush. Members it does not cover compute
-    on their own, as before."""
+    of two launches (``csrc/mc_compute.hip``) instead of one Python wrapper,
+    cache lookup, allocation and launch per metric. The step also performs the
+    curve leader's lazy flush, and the pass that reads the confusion matrix for
+    the scalar members writes the copy a raw ``MulticlassConfusionMatrix`` of
+    the same group returns (``copy_member``: it declares no spec and is not
+    one of ``members``). Members it does not cover compute on their own, as
+    before."""
 
     _STATES = {
         "linear": ("tp", "fp", "tn", "fn"),
@@ -612,13 +615,17 @@ class _FusedMulticlassComputePlan:
         self.members = members
         self.formulas = [p for m, kind, spec, _ in members if kind == "linear"
                          for p in spec[1].params(spec[2])]
+        self.copy_member = None
         self.native = None
         self.steps = 0
 
     @classmethod
     def build(cls, collection) -> "Optional[_FusedMulticlassComputePlan]":
+        from metrics_amd.classification.confusion_matrix import MulticlassConfusionMatrix
+
         leaders: dict = {}
         covered: list = []
+        copy_member = None
         for names in collection._groups.values():
             group = [getattr(collection, n) for n in names]
             specs = [m._compute_plan_spec() for m in group]
@@ -627,8 +634,13 @@ class _FusedMulticlassComputePlan:
             # kind; whatever is left computes on its own
             if len(kinds) != 1 or next(iter(kinds)) in leaders:
                 continue
-            leaders[kinds.pop()] = group[0]
+            kind = kinds.pop()
+            leaders[kind] = group[0]
             covered += [(m, s) for m, s in zip(group, specs) if s is not None]
+            if kind == "confmat_scalar":
+                # an unnormalised confusion matrix returns a copy of the state
+                raw = [m for m in group if type(m) is MulticlassConfusionMatrix and m.normalize in (None, "none")]
+                copy_member = raw[0] if raw else None
         if not covered:
             return None
         # out = [linear 0..n-1 | mcc, kappa, jaccard | exact]
@@ -643,7 +655,9 @@ class _FusedMulticlassComputePlan:
             else:
                 slot = n_linear + 3
             members.append((m, kind, spec, slot))
-        return cls(leaders, members)
+        plan = cls(leaders, members)
+        plan.copy_member = copy_member
+        return plan
 
     def _state_tensors(self, _hip):
         """The leaders' state tensors as the native plan's ``ComputeStates``, or
@@ -726,6 +740,14 @@ class _FusedMulticlassComputePlan:
             ):
                 continue  # not an alias of the leader's states: computes on its own
             todo.append((m, kind, spec, slot))
+        # the raw confusion matrix rides along with a step that runs anyway
+        cm = self.copy_member
+        want_confmat = bool(
+            todo and cm is not None and cm._computed is None and cm.compute_with_cache
+            and cm.confmat is self.leaders["confmat_scalar"].confmat
+            and not cm._is_synced and cm.__dict__.get("_pending_sync_event") is None
+            and not (cm._to_sync and dist.setdefault(cm.distributed_available_fn, cm.distributed_available_fn()))
+        )
         if not todo:
             return True
         native = self.native
@@ -742,8 +764,10 @@ class _FusedMulticlassComputePlan:
             curve.__dict__["_lazy_dirty"] = False  # the step is the flush
             flush = True
         # a histogram the one-pass step left in pending format is completed by the same call
-        out, auc = native.step(flush, _hip.take_b0_pending(curve) if flush else None)
+        out, auc, cm_copy = native.step(flush, _hip.take_b0_pending(curve) if flush else None, want_confmat)
         self.steps += 1
+        if cm_copy is not None:
+            cm._computed = cm_copy.squeeze() if cm_copy.numel() == 1 else cm_copy  # as Metric._wrap_compute
         vals = out.unbind(0)
         for m, kind, spec, slot in todo:
             if kind == "curve_auc":

@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "curve_common.h"
+
 // ---------------------------------------------------------------------------
 // Curve flush: one tile of CTILE classes of the TRANSPOSED (T, C, 2, 2) state.
 //   confmat[t][1][1] += sum_{j>t} hist[j][1]   (tp)
@@ -23,13 +25,23 @@
 // two slots are read by this thread alone (the totals live in suf slot T,
 // which no t < T owns), so the overwrite needs no barrier before it; the
 // caller synchronises before reading the kept values.
+// pending (nullable, with flush only) = [P: C][R: C] of a histogram in
+// pending-b0 format (k_curve_resolve_pending, kernels.hip), thresholds its T
+// float32 thresholds: the staged copy of each class is completed with that
+// kernel's integer identities before the scan, one wave per class,
+//     stage[b0][1] += P[c]          - sum_j stage[j][1]
+//     stage[b0][0] += (R[c] - P[c]) - sum_j stage[j][0]
+// and P[c], R[c] are zeroed. The histogram in memory gets the completed b0
+// words only where it is not zeroed here (zero_hist == 0); no separate pass
+// over it is needed in front of the flush.
 // Block of 256 threads; ends without a barrier.
 template <int CTILE, bool KEEP>
 __device__ __forceinline__ void curve_suffix_tile(
     unsigned long long* __restrict__ hist /* (C, T+1, 2) */, int T, long long C, int zero_hist,
     int flush, long long* __restrict__ confmat /* (T, C, 2, 2) */,
     unsigned long long* __restrict__ stage, unsigned long long* __restrict__ suf, long long c0,
-    int ctile) {
+    int ctile, unsigned long long* __restrict__ pending = nullptr,
+    const float* __restrict__ thresholds = nullptr) {
     typedef long long ll;
     typedef unsigned long long ull;
     const int W = 64;
@@ -42,12 +54,41 @@ __device__ __forceinline__ void curve_suffix_tile(
             if (zero_hist) hist[(c0 + lc) * (ll)row + rem] = 0;
         }
         __syncthreads();
-        // wave-parallel per-class suffix scan: lane partials over T/64 chunks,
-        // cross-lane exclusive suffix via shfl, then a short serial tail per
-        // chunk — serial depth drops from O(T) to O(T/64)+log2(64)
         const int lane = threadIdx.x & (W - 1);
         const int wv = threadIdx.x / W;
         const int nwaves = blockDim.x / W;
+        if (pending) {
+            const int b0 = bucket_of(0.0f, thresholds, T);  // block-uniform
+            // lane l sums the words l, l + 64, ... of the class row: 64 is
+            // even, so a lane keeps to one label; lane 0 ends with label 0,
+            // lane 1 with label 1
+            for (int lc = wv; lc < ctile; lc += nwaves) {
+                ull* h = stage + lc * row;
+                ull sum = 0;
+                for (int j = lane; j < row; j += W) sum += h[j];
+                for (int off = 32; off >= 2; off >>= 1) sum += __shfl_down(sum, off);
+                const ull sum1 = __shfl(sum, 1);
+                if (lane == 0) {
+                    ull* P = pending + (c0 + lc);
+                    ull* R = P + C;
+                    const ull p = *P, r = *R;
+                    const ull v0 = h[b0 * 2 + 0] + ((r - p) - sum);
+                    const ull v1 = h[b0 * 2 + 1] + (p - sum1);
+                    h[b0 * 2 + 0] = v0;
+                    h[b0 * 2 + 1] = v1;
+                    if (!zero_hist) {
+                        hist[(c0 + lc) * (ll)row + b0 * 2 + 0] = v0;
+                        hist[(c0 + lc) * (ll)row + b0 * 2 + 1] = v1;
+                    }
+                    *P = 0;
+                    *R = 0;
+                }
+            }
+            __syncthreads();
+        }
+        // wave-parallel per-class suffix scan: lane partials over T/64 chunks,
+        // cross-lane exclusive suffix via shfl, then a short serial tail per
+        // chunk — serial depth drops from O(T) to O(T/64)+log2(64)
         const int chunk = (T + 1 + W - 1) / W;
         for (int lc = wv; lc < ctile; lc += nwaves) {
             const ull* h = stage + lc * row;

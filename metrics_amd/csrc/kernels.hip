@@ -722,14 +722,18 @@ __global__ void k_curve_suffix(
 template <int CTILE>
 __global__ void k_curve_suffix_tiled(
     unsigned long long* __restrict__ hist /* (C, T+1, 2) */, int T, ll C, int zero_hist,
-    unsigned int* __restrict__ E, ll* __restrict__ confmat /* (T, C, 2, 2) */) {
+    unsigned int* __restrict__ E, ll* __restrict__ confmat /* (T, C, 2, 2) */,
+    unsigned long long* __restrict__ pending /* nullable: [P: C][R: C] */,
+    const float* __restrict__ thresholds) {
     extern __shared__ unsigned long long shs[];
     unsigned long long* stage = shs;                       // CTILE * (T+1) * 2
     unsigned long long* suf = shs + CTILE * (ll)(T + 1) * 2;  // CTILE * (T+1) * 2
     const ll c0 = (ll)blockIdx.x * CTILE;
     const int ctile = (int)min((ll)CTILE, C - c0);
     // the tile body is shared with k_curve_flush_auc (compute_common.h)
-    curve_suffix_tile<CTILE, false>(hist, T, C, zero_hist, 1, confmat, stage, suf, c0, ctile);
+    // a histogram in pending-b0 format is completed in the staged tile
+    curve_suffix_tile<CTILE, false>(hist, T, C, zero_hist, 1, confmat, stage, suf, c0, ctile,
+                                    pending, thresholds);
     if (E && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&E[1], 1u);
 }
 
@@ -1306,16 +1310,14 @@ int ma_curve_resolve_pending(uintptr_t stream, uintptr_t hist, ll C, int T, uint
     return (int)hipGetLastError();
 }
 
-// pending / thresholds: see ma_curve_resolve_pending, which then runs in front
-// of the suffix kernel (both 0 for a histogram that owes nothing)
+// pending / thresholds: see ma_curve_resolve_pending (both 0 for a histogram
+// that owes nothing). The tiled kernel pays what is owed in its staged tile;
+// in front of the one-class-per-block kernel the resolve kernel runs.
 int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int transposed,
                     int zero_hist, uintptr_t epoch_buf, uintptr_t confmat, uintptr_t pending,
                     uintptr_t thresholds) {
     hipStream_t s = (hipStream_t)stream;
-    if (pending) {
-        const int rc = ma_curve_resolve_pending(stream, hist, outer, T, thresholds, pending);
-        if (rc != 0) return rc;
-    }
+    if (pending && (!hist || !thresholds || outer <= 0 || T < 1)) return -103;
     if (transposed) {
         static int ctile_sel = 0;
         if (ctile_sel == 0) {
@@ -1328,19 +1330,26 @@ int ma_curve_suffix(uintptr_t stream, uintptr_t hist, ll outer, int T, int trans
             int grid = (int)((outer + CT - 1) / CT);
             if (CT == 2)
                 k_curve_suffix_tiled<2><<<grid, 256, shmem_t, s>>>(
-                    (unsigned long long*)hist, T, outer, zero_hist, (unsigned int*)epoch_buf, (ll*)confmat);
+                    (unsigned long long*)hist, T, outer, zero_hist, (unsigned int*)epoch_buf,
+                    (ll*)confmat, (unsigned long long*)pending, (const float*)thresholds);
             else if (CT == 4)
                 k_curve_suffix_tiled<4><<<grid, 256, shmem_t, s>>>(
-                    (unsigned long long*)hist, T, outer, zero_hist, (unsigned int*)epoch_buf, (ll*)confmat);
+                    (unsigned long long*)hist, T, outer, zero_hist, (unsigned int*)epoch_buf,
+                    (ll*)confmat, (unsigned long long*)pending, (const float*)thresholds);
             else
                 k_curve_suffix_tiled<8><<<grid, 256, shmem_t, s>>>(
-                    (unsigned long long*)hist, T, outer, zero_hist, (unsigned int*)epoch_buf, (ll*)confmat);
+                    (unsigned long long*)hist, T, outer, zero_hist, (unsigned int*)epoch_buf,
+                    (ll*)confmat, (unsigned long long*)pending, (const float*)thresholds);
             return (int)hipGetLastError();
         }
     }
     // k_curve_suffix also holds two static __shared__ u64 totals
     size_t shmem = (size_t)(T + 1) * 2 * sizeof(unsigned long long);
     if (shmem + 2 * sizeof(unsigned long long) > 160 * 1024) return -100;
+    if (pending) {
+        const int rc = ma_curve_resolve_pending(stream, hist, outer, T, thresholds, pending);
+        if (rc != 0) return rc;
+    }
     k_curve_suffix<<<(int)outer, 256, shmem, s>>>((unsigned long long*)hist, T, outer, transposed,
                                                   zero_hist, (unsigned int*)epoch_buf,
                                                   (ll*)confmat);

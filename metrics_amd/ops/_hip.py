@@ -306,7 +306,9 @@ _SIGNATURES = {
     "ma_confmat_scalars": [_U64, _U64, _LL, _U64, ctypes.c_float, _U64],
     "ma_confmat_moments": [_U64, _U64, _LL, _U64],
     "ma_compute_plan_create": [_LL, _I, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _I, _F, _LL, ctypes.POINTER(ctypes.c_ulonglong)],
-    "ma_compute_plan_step": [_U64, _U64, _I, _U64, _U64, _U64, _U64],
+    "ma_compute_plan_step": [_U64, _U64, _I, _U64, _U64, _U64, _U64, _U64],
+    "ma_compute_plan_launches": [_U64, _I, _I],
+    "ma_confmat_moments_copy": [_U64, _U64, _LL, _U64, _U64],
     "ma_linear_stat_multi": [_U64, _U64, _U64, _U64, _U64, _LL, _I, _U64, _U64],
     "ma_mc_onepass_nv": [_I, _LL, _I],
     "ma_mc_onepass_lpr": [_I, _LL, _I],
@@ -2066,6 +2068,48 @@ def curve_resolve_pending(hist: Tensor, thresholds: Tensor, pending: Optional[Te
     _check(rc, "ma_curve_resolve_pending")
 
 
+def curve_suffix_flush(hist: Tensor, confmat: Tensor, thresholds: Optional[Tensor] = None,
+                       pending: Optional[Tensor] = None, zero_hist: bool = True) -> None:
+    """The stand-alone flush alone (``ma_curve_suffix``): add the (C, T+1, 2)
+    int64 ``hist`` into the transposed (T, C, 2, 2) int64 ``confmat`` state.
+    ``pending`` = [P: C][R: C] of a histogram in pending-b0 format, with its
+    float32 ``thresholds``: completed by the same kernel and zeroed."""
+    C, T = hist.shape[0], hist.shape[1] - 1
+    assert hist.is_contiguous() and hist.dtype == torch.long
+    assert confmat.is_contiguous() and confmat.dtype == torch.long and confmat.shape == (T, C, 2, 2)
+    if pending is not None:
+        assert pending.is_contiguous() and pending.dtype == torch.long and pending.numel() >= 2 * C
+        assert thresholds.is_contiguous() and thresholds.dtype == torch.float32 and thresholds.numel() == T
+    rc = _lib().ma_curve_suffix(
+        _stream(), hist.data_ptr(), C, T, 1, 1 if zero_hist else 0, 0, confmat.data_ptr(),
+        pending.data_ptr() if pending is not None else 0,
+        thresholds.data_ptr() if pending is not None else 0,
+    )
+    _check(rc, "ma_curve_suffix")
+
+
+def confmat_moments_copy(confmat: Tensor, scratch: Tensor, copy: Optional[Tensor] = None) -> None:
+    """One pass over the (C, C) int64 ``confmat`` (``ma_confmat_moments_copy``):
+    row sums, column sums and diagonal into the zeroed 3C int64 ``scratch``
+    [tk | pk | diag] and, when given, a copy of the matrix into ``copy``."""
+    C = confmat.shape[0]
+    assert confmat.is_contiguous() and confmat.dtype == torch.long and confmat.shape == (C, C)
+    assert scratch.is_contiguous() and scratch.dtype == torch.long and scratch.numel() >= 3 * C
+    assert copy is None or (copy.is_contiguous() and copy.dtype == torch.long and copy.shape == (C, C))
+    rc = _lib().ma_confmat_moments_copy(
+        _stream(), confmat.data_ptr(), C, scratch.data_ptr(), copy.data_ptr() if copy is not None else 0
+    )
+    _check(rc, "ma_confmat_moments_copy")
+
+
+def confmat_moments(confmat: Tensor, scratch: Tensor) -> None:
+    """The stand-alone moments kernel (``ma_confmat_moments``), same scratch."""
+    C = confmat.shape[0]
+    assert confmat.is_contiguous() and confmat.dtype == torch.long and confmat.shape == (C, C)
+    assert scratch.is_contiguous() and scratch.dtype == torch.long and scratch.numel() >= 3 * C
+    _check(_lib().ma_confmat_moments(_stream(), confmat.data_ptr(), C, scratch.data_ptr()), "ma_confmat_moments")
+
+
 def onepass_scratch_layout(num_classes: int) -> dict:
     """Offsets in u64 words of the one-pass curve scratch, as the Python side
     reads it: ``P`` and ``R`` (``num_classes`` words each) lead, the per-block
@@ -3052,21 +3096,36 @@ class _ComputePlan(_NativePlan):
         self.owned = (params_dev, cm_scratch, auc)
         self.n_formulas = n
 
-    def step(self, flush: bool, pending: Optional[tuple] = None):
-        """One native call, at most three launches, one more in front of them
-        for ``pending`` = (curve scratch, float32 thresholds) of a histogram in
-        pending-b0 format (:func:`take_b0_pending`; with ``flush`` only). Returns (out, auc): a fresh
-        ``[linear 0..n-1 | mcc, kappa, jaccard | exact]`` float32 buffer and the
+    def step(self, flush: bool, pending: Optional[tuple] = None, want_confmat: bool = False):
+        """One native call of two launches (:meth:`launches`). ``pending`` =
+        (curve scratch, float32 thresholds) of a histogram in pending-b0 format
+        (:func:`take_b0_pending`; with ``flush`` only) is completed by the
+        flush itself. Returns (out, auc, confmat): a fresh
+        ``[linear 0..n-1 | mcc, kappa, jaccard | exact]`` float32 buffer, the
         (C,) views ``(auroc, auroc weights, ap, ap weights)`` of the plan's own
         per-class buffer (None without a curve group; overwritten by the next
-        step, so only reductions of them go to a caller)."""
+        step, so only reductions of them go to a caller) and, for
+        ``want_confmat``, a fresh (C, C) copy of the confusion matrix written
+        by the pass that reads it for the moments (else None)."""
         _, _, auc = self.owned
         # fresh per compute: views of it go to the caller and are never recycled
         out = torch.empty(self.n_formulas + 4, dtype=torch.float32, device=self.device)
+        cm_copy = torch.empty_like(self.tensors.confmat) if want_confmat else None
         rc = _lib().ma_compute_plan_step(
             self.handle, _stream(), COMPUTE_FLUSH if flush else 0, out.data_ptr(),
             auc.data_ptr() if auc is not None else 0,
             pending[0].data_ptr() if pending else 0, pending[1].data_ptr() if pending else 0,
+            cm_copy.data_ptr() if want_confmat else 0,
         )
         _check(rc, "ma_compute_plan_step")
-        return out, self.auc_views
+        return out, self.auc_views, cm_copy
+
+    def launches(self, flush: bool, pending: bool) -> int:
+        """Kernel launches :meth:`step` makes for these flags. Host only."""
+        return compute_plan_launches(self.handle, flush, pending)
+
+
+def compute_plan_launches(handle: int, flush: bool, pending: bool) -> int:
+    """``ma_compute_plan_launches``: the launch count of one step of the
+    native plan ``handle``; negative where the step would be refused."""
+    return int(_lib().ma_compute_plan_launches(handle, COMPUTE_FLUSH if flush else 0, int(bool(pending))))
