@@ -33,6 +33,31 @@ def _format_inputs(preds: Tensor, target: Tensor, num_classes: int, input_format
     return preds, target
 
 
+def _overlap_counts(
+    preds: Tensor, target: Tensor, num_classes: int, include_background: bool, input_format: str
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """Per-sample per-class (intersection, pred_sum, target_sum), int64."""
+    if preds.is_cuda:
+        # csrc/seg_overlap.hip: one counting pass over the inputs as they are;
+        # None where it does not cover the call (the chain below runs)
+        from metrics_amd.ops import _hip
+
+        record = _hip.seg_overlap(preds, target, num_classes, input_format)
+        if record is not None:
+            if not include_background and record.shape[2] > 1:
+                record = record[:, :, 1:]
+            return record[0], record[1], record[2]
+    preds, target = _format_inputs(preds, target, num_classes, input_format)
+    if not include_background:
+        preds, target = _ignore_background(preds, target)
+
+    reduce_axis = list(range(2, preds.ndim))
+    intersection = torch.sum(preds * target, dim=reduce_axis)
+    target_sum = torch.sum(target, dim=reduce_axis)
+    pred_sum = torch.sum(preds, dim=reduce_axis)
+    return intersection, pred_sum, target_sum
+
+
 def _mean_iou_update(
     preds: Tensor,
     target: Tensor,
@@ -44,14 +69,7 @@ def _mean_iou_update(
     _check_input_format(input_format)
     if input_format in ("index", "mixed") and num_classes is None:
         raise ValueError("Argument `num_classes` must be provided when `input_format` is 'index' or 'mixed'")
-    preds, target = _format_inputs(preds, target, num_classes, input_format)
-    if not include_background:
-        preds, target = _ignore_background(preds, target)
-
-    reduce_axis = list(range(2, preds.ndim))
-    intersection = torch.sum(preds * target, dim=reduce_axis)
-    target_sum = torch.sum(target, dim=reduce_axis)
-    pred_sum = torch.sum(preds, dim=reduce_axis)
+    intersection, pred_sum, target_sum = _overlap_counts(preds, target, num_classes, include_background, input_format)
     union = target_sum + pred_sum - intersection
     return intersection, union
 
@@ -88,14 +106,7 @@ def _dice_score_update(
     input_format: str = "one-hot",
 ) -> Tuple[Tensor, Tensor, Tensor]:
     _check_input_format(input_format)
-    preds, target = _format_inputs(preds, target, num_classes, input_format)
-    if not include_background:
-        preds, target = _ignore_background(preds, target)
-
-    reduce_axis = list(range(2, preds.ndim))
-    intersection = torch.sum(preds * target, dim=reduce_axis)
-    target_sum = torch.sum(target, dim=reduce_axis)
-    pred_sum = torch.sum(preds, dim=reduce_axis)
+    intersection, pred_sum, target_sum = _overlap_counts(preds, target, num_classes, include_background, input_format)
 
     numerator = 2 * intersection
     denominator = pred_sum + target_sum
@@ -147,14 +158,7 @@ def generalized_dice_score(
     _check_input_format(input_format)
     if weight_type not in ("square", "simple", "linear"):
         raise ValueError(f"Expected argument `weight_type` to be one of 'square', 'simple', 'linear', but got {weight_type}")
-    preds, target = _format_inputs(preds, target, num_classes, input_format)
-    if not include_background:
-        preds, target = _ignore_background(preds, target)
-
-    reduce_axis = list(range(2, preds.ndim))
-    intersection = torch.sum(preds * target, dim=reduce_axis)
-    target_sum = torch.sum(target, dim=reduce_axis)
-    pred_sum = torch.sum(preds, dim=reduce_axis)
+    intersection, pred_sum, target_sum = _overlap_counts(preds, target, num_classes, include_background, input_format)
 
     if weight_type == "simple":
         weights = 1.0 / target_sum

@@ -335,6 +335,8 @@ _SIGNATURES = {
     "ma_hausdorff_count": [_U64, _U64, _I, _I, _U64, _I, _I, _LL, _LL, _LL, _LL, _U64],
     "ma_hausdorff_run": [_U64, _U64, _I, _I, _U64, _I, _I, _LL, _LL, _LL, _LL, _U64, _U64, _LL, _LL, _U64, _I, _I,
                          _F, _F, _U64, _U64],
+    "ma_seg_overlap_layout": [_LL, _LL, _LL, _I, _I, ctypes.POINTER(_LL)],
+    "ma_seg_overlap": [_U64, _U64, _I, _I, _U64, _I, _I, _LL, _LL, _LL, _U64],
     "ma_kendall_layout": [_LL, _LL, ctypes.POINTER(_LL)],
     "ma_kendall": [_U64, _U64, _U64, _I, _LL, _LL, _I, _U64, ctypes.c_ulonglong, _U64, _U64],
     "ma_spearman_layout": [_LL, _LL, ctypes.POINTER(_LL)],
@@ -1343,6 +1345,114 @@ def hausdorff_distance(
     _check(rc, "ma_hausdorff_run")
     _HD_CALLS += 1
     return out.view(N, C - c0)
+
+
+# Segmentation overlap counts (csrc/seg_overlap.hip): intersection, pred_sum and
+# target_sum of every (sample, class) in one pass over label maps or one-hot
+# planes as they are, no one-hot tensor and no host sync.
+# METRICS_AMD_SEG_OVERLAP_KERNEL=0 keeps the torch chain of
+# functional/segmentation/metrics.py everywhere (A/B lever, escape hatch). Read
+# at every call.
+SEG_OVERLAP_KERNEL_ENV = "METRICS_AMD_SEG_OVERLAP_KERNEL"
+
+# Largest number of classes (3 * C LDS counters for each wave of a block),
+# elements of a block's chunk, largest S of the wave-per-sample mapping, merge
+# rounds before the plain-atomic fall-through, samples of a block in the wave
+# mapping and the cap of the grid (SO_MAX_C, SO_CHUNK, SO_SMALL_S, SO_ROUNDS,
+# SO_WAVES, SO_MAX_GRID in csrc/seg_overlap.hip; seg_overlap_layout holds the
+# two together).
+SEG_OVERLAP_MAX_C = 1024
+SEG_OVERLAP_CHUNK = 8192
+SEG_OVERLAP_SMALL_S = 4096
+SEG_OVERLAP_ROUNDS = 4
+SEG_OVERLAP_WAVES = 4
+SEG_OVERLAP_MAX_GRID = 16384
+
+_SO_LABEL_DTYPES = {torch.uint8: 1, torch.int32: 2, torch.int64: 3}
+_SO_PLANE_DTYPES = {torch.bool: 0, torch.uint8: 1, torch.int64: 3}
+_SO_LAYOUT_CACHE: dict = {}
+_SO_CALLS = 0
+
+
+def seg_overlap_kernel_enabled() -> bool:
+    return os.environ.get(SEG_OVERLAP_KERNEL_ENV, "1") != "0"
+
+
+def seg_overlap_kernel_calls() -> int:
+    """How many calls the overlap kernels have served in this process."""
+    return _SO_CALLS
+
+
+def seg_overlap_layout(N: int, C: int, S: int, p_planes: bool = False, t_planes: bool = False) -> Optional[tuple]:
+    """(largest C, chunk, largest S of the wave mapping, merge rounds, samples
+    of a block in the wave mapping, grid cap, mapping of this call (0 chunk,
+    1 wave per sample, 2 planes), blocks, bytes of LDS) of a call over N samples,
+    C classes and S elements per plane; None where the kernels do not cover it
+    (N, C or S zero, C above the largest). Host only."""
+    key = (N, C, S, bool(p_planes), bool(t_planes))
+    if key not in _SO_LAYOUT_CACHE:
+        out = (_LL * 9)()
+        rc = _lib().ma_seg_overlap_layout(N, C, S, int(p_planes), int(t_planes), out)
+        shared = (SEG_OVERLAP_MAX_C, SEG_OVERLAP_CHUNK, SEG_OVERLAP_SMALL_S, SEG_OVERLAP_ROUNDS, SEG_OVERLAP_WAVES,
+                  SEG_OVERLAP_MAX_GRID)
+        if tuple(out[:6]) != shared:
+            raise RuntimeError(
+                f"csrc/seg_overlap.hip: class cap, chunk, mapping boundary, rounds, waves and grid cap {tuple(out[:6])}"
+                " differ from the Python constants; rebuild the library"
+            )
+        if len(_SO_LAYOUT_CACHE) > 256:
+            _SO_LAYOUT_CACHE.clear()
+        _SO_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _SO_LAYOUT_CACHE[key]
+
+
+def seg_overlap(preds: Tensor, target: Tensor, num_classes: Optional[int], input_format: str) -> Optional[Tensor]:
+    """The ``(3, N, C)`` int64 record ``[intersection | pred_sum | target_sum]``
+    of a call of ``mean_iou`` / ``dice_score`` / ``generalized_dice_score`` on
+    the current stream, with no host sync. A label outside ``[0, C)`` is counted
+    in no class.
+
+    Returns None without launching anything where the kernels do not cover the
+    call: CPU tensors or two devices, a float side (labels are uint8 / int32 /
+    int64, planes bool / uint8 / int64), an ``ndim`` pair that does not fit the
+    format, batch or spatial shapes that disagree, one-hot planes whose ``C``
+    disagrees with ``num_classes`` in ``mixed``, a call outside
+    ``seg_overlap_layout``, or the switch off.
+    """
+    global _SO_CALLS
+    if not seg_overlap_kernel_enabled() or not (preds.is_cuda and target.device == preds.device):
+        return None
+    d = preds.ndim - target.ndim
+    if d not in {"index": (0,), "one-hot": (0,), "mixed": (1, -1)}[input_format]:
+        return None
+    planes = (True, True) if input_format == "one-hot" else (d == 1, d == -1)
+    if preds.ndim - planes[0] < 2:  # a batch and at least one spatial dimension
+        return None
+    C = None if planes == (True, True) else num_classes
+    spatial = []
+    for x, pl in zip((preds, target), planes):
+        if x.dtype not in (_SO_PLANE_DTYPES if pl else _SO_LABEL_DTYPES):
+            return None
+        if pl:
+            if C is not None and x.shape[1] != C:
+                return None
+            C = x.shape[1]
+        spatial.append((x.shape[0], *x.shape[1 + pl:]))
+    if spatial[0] != spatial[1] or not isinstance(C, int):
+        return None
+    N, S = spatial[0][0], math.prod(spatial[0][1:])
+    if seg_overlap_layout(N, C, S, *planes) is None:
+        return None
+    preds, target = preds.contiguous(), target.contiguous()
+    out = torch.zeros(3, N, C, dtype=torch.int64, device=preds.device)
+    codes = [(_SO_PLANE_DTYPES if pl else _SO_LABEL_DTYPES)[x.dtype] for x, pl in zip((preds, target), planes)]
+    rc = _lib().ma_seg_overlap(_stream(), preds.data_ptr(), int(planes[0]), codes[0], target.data_ptr(),
+                               int(planes[1]), codes[1], N, C, S, out.data_ptr())
+    if rc == -103:
+        return None  # nothing was launched
+    _check(rc, "ma_seg_overlap")
+    _SO_CALLS += 1
+    return out
 
 
 # Kendall rank correlation (csrc/kendall.hip): the pair counts of every column
