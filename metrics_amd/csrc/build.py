@@ -28,10 +28,12 @@ ARCH = os.environ.get("METRICS_AMD_ARCH", "gfx950")
 # and so is spearman.hip (integer rank sums, an fp64 tail). mc_compute.hip: its
 # two-role kernel is integer work around the per-lane fp32 terms of the AUC sums.
 # seg_overlap.hip is integer counting only and is built the same way.
+# pairwise_lp.hip keeps one fp32 accumulator per output element, each term
+# rounded on its own, and is built the same way.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 OWN_FLAGS = {"lm_nll.hip": NO_PACKED_FP32, "retrieval_score.hip": NO_PACKED_FP32, "hausdorff.hip": NO_PACKED_FP32,
              "kendall.hip": NO_PACKED_FP32, "spearman.hip": NO_PACKED_FP32, "mc_compute.hip": NO_PACKED_FP32,
-             "seg_overlap.hip": NO_PACKED_FP32}
+             "seg_overlap.hip": NO_PACKED_FP32, "pairwise_lp.hip": NO_PACKED_FP32}
 
 
 def build(verbose: bool = True) -> Path:

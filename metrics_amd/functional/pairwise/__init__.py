@@ -1,7 +1,9 @@
 """Pairwise similarity/distance functions.
 
-Parity: torchmetrics ``functional/pairwise/*`` — matmul-shaped, so these ride
-hipBLASLt via torch.matmul (fp32 accumulate through _safe_matmul).
+Parity: torchmetrics ``functional/pairwise/*``. Cosine, linear and euclidean are
+matmul-shaped and ride hipBLASLt via torch.matmul (fp32 accumulate through
+_safe_matmul); Manhattan and Minkowski are not bilinear and run in the tiled
+kernel of csrc/pairwise_lp.hip on CUDA inputs.
 """
 from __future__ import annotations
 
@@ -13,7 +15,7 @@ from torch import Tensor
 from metrics_amd.utilities.compute import _safe_matmul
 
 
-def _check_input(x: Tensor, y: Optional[Tensor], zero_diagonal: Optional[bool]) -> tuple:
+def _check_input(x: Tensor, y: Optional[Tensor], zero_diagonal: Optional[bool], clone: bool = True) -> tuple:
     if x.ndim != 2:
         raise ValueError(f"Expected argument `x` to be a 2D tensor of shape `[N, d]` but got {x.shape}")
     if y is not None:
@@ -24,9 +26,20 @@ def _check_input(x: Tensor, y: Optional[Tensor], zero_diagonal: Optional[bool]) 
             )
         zero_diagonal = False if zero_diagonal is None else zero_diagonal
     else:
-        y = x.clone()
+        y = x.clone() if clone else x
         zero_diagonal = True if zero_diagonal is None else zero_diagonal
     return x, y, zero_diagonal
+
+
+def _lp_kernel(x: Tensor, y: Tensor, exponent: float, zero_diagonal: bool, reduction: Optional[str]) -> Optional[Tensor]:
+    """csrc/pairwise_lp.hip: one tiled pass, no (N, M, D) temporary and with a
+    reduction no (N, M) matrix; None where it does not cover the call (the
+    torch chain runs)."""
+    if not x.is_cuda:
+        return None
+    from metrics_amd.ops import _hip
+
+    return _hip.pairwise_lp(x, y, exponent, zero_diagonal, reduction)
 
 
 def _reduce_distance_matrix(distmat: Tensor, reduction: Optional[str] = None) -> Tensor:
@@ -86,7 +99,13 @@ def pairwise_manhattan_distance(
     x: Tensor, y: Optional[Tensor] = None, reduction: Optional[str] = None, zero_diagonal: Optional[bool] = None
 ) -> Tensor:
     """Pairwise manhattan distance (N, M)."""
-    x, y, zero_diagonal = _check_input(x, y, zero_diagonal)
+    same = y is None
+    x, y, zero_diagonal = _check_input(x, y, zero_diagonal, clone=False)
+    distance = _lp_kernel(x, y, 1, zero_diagonal, reduction)
+    if distance is not None:
+        return distance
+    if same:
+        y = x.clone()
     distance = (x.unsqueeze(1) - y.unsqueeze(0).repeat(x.shape[0], 1, 1)).abs().sum(dim=-1)
     if zero_diagonal:
         distance.fill_diagonal_(0)
@@ -98,9 +117,15 @@ def pairwise_minkowski_distance(
     zero_diagonal: Optional[bool] = None,
 ) -> Tensor:
     """Pairwise minkowski distance of order ``exponent`` (N, M)."""
-    x, y, zero_diagonal = _check_input(x, y, zero_diagonal)
+    same = y is None
+    x, y, zero_diagonal = _check_input(x, y, zero_diagonal, clone=False)
     if not (isinstance(exponent, (float, int)) and exponent > 0):
         raise ValueError(f"Argument `exponent` must be a positive int or float but got {exponent}")
+    distance = _lp_kernel(x, y, exponent, zero_diagonal, reduction)
+    if distance is not None:
+        return distance
+    if same:
+        y = x.clone()
     distance = (x.unsqueeze(1) - y.unsqueeze(0)).abs().pow(exponent).sum(-1).pow(1.0 / exponent)
     if zero_diagonal:
         distance.fill_diagonal_(0)

@@ -341,6 +341,8 @@ _SIGNATURES = {
     "ma_kendall": [_U64, _U64, _U64, _I, _LL, _LL, _I, _U64, ctypes.c_ulonglong, _U64, _U64],
     "ma_spearman_layout": [_LL, _LL, ctypes.POINTER(_LL)],
     "ma_spearman": [_U64, _U64, _U64, _I, _LL, _LL, _U64, ctypes.c_ulonglong, _U64, _U64],
+    "ma_pairwise_lp_layout": [_LL, _LL, _LL, ctypes.POINTER(_LL)],
+    "ma_pairwise_lp": [_U64, _U64, _U64, _I, _LL, _LL, _LL, _D, _I, _I, _U64, _U64],
 }
 
 
@@ -1696,6 +1698,106 @@ def spearman_ranks(preds: Tensor, target: Tensor, owner=None) -> Optional[Spearm
     _check(rc, "ma_spearman")
     _SP_CALLS += 1
     return SpearmanResult(record, rho)
+
+
+# Pairwise L_p distances (csrc/pairwise_lp.hip): pairwise_manhattan_distance
+# and pairwise_minkowski_distance in one tiled kernel, no (N, M, D) temporary,
+# and with a reduction no (N, M) matrix either. No host sync.
+# METRICS_AMD_PAIRWISE_KERNEL=0 keeps the torch chain of
+# functional/pairwise/__init__.py everywhere (A/B lever, escape hatch). Read at
+# every call.
+PAIRWISE_KERNEL_ENV = "METRICS_AMD_PAIRWISE_KERNEL"
+
+# Rows of x and rows of y of a block's output tile, k of a staged chunk and
+# lanes of a block (LP_TN, LP_TM, LP_KC, LP_BLOCK in csrc/pairwise_lp.hip;
+# pairwise_lp_layout holds the two together).
+PAIRWISE_TILE_N = 128
+PAIRWISE_TILE_M = 128
+PAIRWISE_CHUNK_K = 16
+PAIRWISE_BLOCK = 256
+
+_LP_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_LP_REDUCTIONS = {None: 0, "none": 0, "sum": 1, "mean": 2}
+_LP_LAYOUT_CACHE: dict = {}
+_LP_CALLS = 0
+
+
+def pairwise_kernel_enabled() -> bool:
+    return os.environ.get(PAIRWISE_KERNEL_ENV, "1") != "0"
+
+
+def pairwise_kernel_calls() -> int:
+    """How many calls the pairwise L_p kernel has served in this process."""
+    return _LP_CALLS
+
+
+def pairwise_lp_layout(N: int, M: int, D: int) -> Optional[tuple]:
+    """(tile rows, tile columns, k of a chunk, lanes of a block, row tiles,
+    column tiles, blocks, bytes of LDS of a block, fp32 words of the partial
+    buffer of a reduced call) of a call over x (N, D) and y (M, D); None where
+    the kernel does not cover it (an empty dimension, more tiles than a grid
+    holds). Host only."""
+    key = (N, M, D)
+    if key not in _LP_LAYOUT_CACHE:
+        out = (_LL * 9)()
+        rc = _lib().ma_pairwise_lp_layout(N, M, D, out)
+        shared = (PAIRWISE_TILE_N, PAIRWISE_TILE_M, PAIRWISE_CHUNK_K, PAIRWISE_BLOCK)
+        if tuple(out[:4]) != shared:
+            raise RuntimeError(
+                f"csrc/pairwise_lp.hip: tile sides, chunk and block {tuple(out[:4])} differ from the Python constants;"
+                " rebuild the library"
+            )
+        if len(_LP_LAYOUT_CACHE) > 256:
+            _LP_LAYOUT_CACHE.clear()
+        _LP_LAYOUT_CACHE[key] = tuple(out) if rc == 0 else None
+    return _LP_LAYOUT_CACHE[key]
+
+
+def pairwise_lp(x: Tensor, y: Tensor, exponent: float, zero_diagonal: bool, reduction: Optional[str]) -> Optional[Tensor]:
+    """``(sum_k |x[i, k] - y[j, k]| ** exponent) ** (1 / exponent)`` of ``x``
+    ``(N, D)`` against ``y`` ``(M, D)`` (``y`` may be ``x`` itself) on the current
+    stream: ``(N, M)`` in the input dtype, or ``(N,)`` row sums / means of the
+    rounded elements with ``reduction`` ``"sum"`` / ``"mean"``. ``zero_diagonal``
+    writes 0 where ``i == j``. fp32 accumulation in ascending ``k``; a repeated
+    call gives the same bits. No host sync.
+
+    Returns None without launching anything where the kernel does not cover the
+    call: CPU tensors or two devices, fp64 or integer inputs, mixed dtypes, an
+    exponent that is not a finite positive number, an unknown reduction, inputs
+    that are not 2-D with one ``D``, an empty dimension, a call outside
+    ``pairwise_lp_layout``, autograd enabled and an input that requires grad
+    (the torch chain carries the graph), or the switch off.
+    """
+    global _LP_CALLS
+    if not pairwise_kernel_enabled() or not (x.is_cuda and y.device == x.device):
+        return None
+    if x.dtype not in _LP_DTYPES or y.dtype != x.dtype:
+        return None
+    if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return None
+    if isinstance(exponent, bool) or not isinstance(exponent, (int, float)) or not 0 < exponent < math.inf:
+        return None
+    if not isinstance(reduction, (str, type(None))) or reduction not in _LP_REDUCTIONS:
+        return None
+    if x.ndim != 2 or y.ndim != 2 or x.shape[1] != y.shape[1]:
+        return None
+    (N, D), M = x.shape, y.shape[0]
+    lay = pairwise_lp_layout(N, M, D) if N and M and D else None
+    if lay is None:
+        return None
+    same = y is x
+    x = x.contiguous()
+    y = x if same else y.contiguous()
+    red = _LP_REDUCTIONS[reduction]
+    out = torch.empty((N, M) if red == 0 else (N,), dtype=x.dtype, device=x.device)
+    partial = torch.empty(lay[8], dtype=torch.float32, device=x.device) if red else None
+    rc = _lib().ma_pairwise_lp(_stream(), x.data_ptr(), y.data_ptr(), _LP_DTYPES[x.dtype], N, M, D, float(exponent),
+                               int(bool(zero_diagonal)), red, out.data_ptr(), partial.data_ptr() if red else 0)
+    if rc == -103:
+        return None  # nothing was launched
+    _check(rc, "ma_pairwise_lp")
+    _LP_CALLS += 1
+    return out
 
 
 _ERR_OPS = {"sq_err": (0, 1), "abs_err": (1, 1), "ape": (2, 1), "sq_log_err": (3, 1), "moments": (4, 6), "logcosh": (5, 1)}
